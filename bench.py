@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- QPS @ recall@10 >= 0.95, 1M x 384 Vamana search, batch = 1024 (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--mode shards|replicas|c5] [--config c2|c3|c4]
+    python bench.py --gpus N --steps K --warmup W [--mode shards|replicas|c5] [--config c2|c3|c4] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one batch of 1024 synthetic queries through the GPU-resident greedy search
 (IndexVamana.Search semantics, searchSize 75, degreeBound 64, alpha 1.2, cosine, k = 10) with the
@@ -34,6 +35,15 @@ The JSON line also carries:
 
 --config c3 reports the build (inserts/s) and --config c4 the product-quantized search (10M x 768) as the
 value; both are secondary configurations, the driver runs the default.
+
+A plain run does what the headline needs and no more: data, build, the recall gate, warmup, the timed steps and the
+line (metric, value, unit, higher_is_better, dtype, ms_per_step, recall_at_10 ...).  Everything else above -- roofline
+and its counter pass, build_roofline, the flat-scan cross-check, the second timed pass, two batches in flight, host
+rates, side kernels, latency, the CPU baseline, the two-precision hop, the secondary datasets, the C4 point and, for
+N > 1, the exchange-alone timing -- runs only with --full.
+  --dump-outputs DIR  after the timed steps, the answers of the last timed step (ids, dists, counts; shards when the
+                      exchange merged them) as DIR/<name>.npy in float64 / float32 (C2 only).  The inputs are seeded,
+                      so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -304,7 +314,13 @@ def main():
     ap.add_argument("--no-host-rates", action="store_true")
     ap.add_argument("--cpu-repeat", type=int, default=2)
     ap.add_argument("--pq-m", default="8,192", help="c4: sub-vector counts to measure")
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement and check beyond the headline (roofline, baselines, other datasets, C4 ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's answers as DIR/<name>.npy (float32 / float64)")
     a = ap.parse_args()
+    if a.dump_outputs and a.config != "c2":
+        ap.error("--dump-outputs: the C2 search only")
     if a.rows is None:
         a.rows = 10_000_000 if a.config == "c4" else 1_000_000
     if a.dim is None:
@@ -392,13 +408,14 @@ def run_c2(a, ctx):
             walls.append("%s: %s" % (m, cfg["wall_s_by_phase"]))
             res["config"]["%s_qps" % m] = r["value"]  # scalars: nested objects do not survive the driver's record
             res["config"]["%s_recall_at_10" % m] = cfg["recall_at_10"]
-            res["config"]["%s_roofline_frac" % m] = r["roofline"]["frac"]
+            if "roofline" in r:  # --full
+                res["config"]["%s_roofline_frac" % m] = r["roofline"]["frac"]
             modes[m] = {"value": r["value"], "unit": r["unit"], "ms_per_step": r["ms_per_step"], "scaling": r["scaling"],
                         "workload": cfg["workload"], "parallelism": cfg["parallelism"], "dataset": cfg["dataset"],
-                        "recall_at_10": cfg["recall_at_10"], "build_s": cfg["build_s"], "mean_n_dist": cfg["mean_n_dist"],
+                        "recall_at_10": cfg["recall_at_10"], "build_s": cfg["build_s"], "mean_n_dist": cfg.get("mean_n_dist"),
                         "exchange": cfg.get("exchange"), "exchange_transport": cfg.get("exchange_transport"),
                         "ranks_seen": cfg.get("ranks_seen"),
-                        "per_shard_walk_qps": cfg.get("per_shard_walk_qps"), "roofline": r["roofline"]}
+                        "per_shard_walk_qps": cfg.get("per_shard_walk_qps"), "roofline": r.get("roofline")}
             if r.get("invalid"):
                 modes[m]["invalid"] = r["invalid"]
         res["config"]["primary_mode"] = "shards"
@@ -414,7 +431,6 @@ def run_c2(a, ctx):
 
 
 def measure_mode(a, ctx, mode, rows, primary):
-    from semadb_amd import flat
     rank, world, dev, dev_index = ctx["rank"], ctx["world"], ctx["dev"], ctx["dev_index"]
     use_dist, dist, barrier = ctx["use_dist"], ctx["dist"], ctx["barrier"]
     d, nq, k, L = a.dim, a.batch, a.k, a.search_size
@@ -452,7 +468,7 @@ def measure_mode(a, ctx, mode, rows, primary):
     ix, build_s = build_index(a, base, dev_index)
     phase("build")
     n_nodes, n_edges, _ = ix.stats()
-    broof = build_roofline(ix, n, d, build_s)
+    broof = build_roofline(ix, n, d, build_s) if a.full else None
     log("rank %d: data %.1fs, build %.2fs (%.0f inserts/s), avg degree %.2f" %
         (rank, t1 - t0, build_s, n / build_s, n_edges / n_nodes))
 
@@ -512,20 +528,9 @@ def measure_mode(a, ctx, mode, rows, primary):
         total += nq * k
     recall = hits / total
     log("recall@%d = %.4f at searchSize %d (%d queries)" % (k, recall, L, total // k))
-    # cross-check of the ground truth itself: the device flat scan (IndexFlat.Search, flat.go:76-132, same
-    # bit-exact distances) against the torch matmul top-k, first batch, this rank's shard
-    f_ids, _, _ = flat.flat_search_batch(ix._h, d, queries[0], k, device=dev_index)
-    t_ids = exact_topk(queries[0], base, k)[1] + 2
-    truth_agree = float((f_ids.to(torch.int64).unsqueeze(2) == t_ids.unsqueeze(1)).any(2).float().mean().item())
-    log("flat scan vs matmul ground truth agreement: %.4f" % truth_agree)
-    # the exact scan as a measured point of its own (IndexFlat.Search of one query batch over this rank's rows)
-    torch.cuda.synchronize()
-    t_f = time.perf_counter()
-    for _ in range(3):
-        flat.flat_search_batch(ix._h, d, queries[0], k, device=dev_index)
-    torch.cuda.synchronize()
-    flat_ms = (time.perf_counter() - t_f) / 3 * 1e3
-    log("flat exact scan: %.2f ms per %d queries over %d rows" % (flat_ms, nq, n))
+    truth_agree = flat_ms = None
+    if a.full:
+        truth_agree, flat_ms = flat_scan_point(ix, queries, base, d, k, nq, n, dev_index)
 
     phase("recall+scan")
     # ---- timed region: batches the recall phase never walked, trace counters OFF, one batch at a time
@@ -558,22 +563,27 @@ def measure_mode(a, ctx, mode, rows, primary):
     kernel_ms = ix.profile_read()[-a.steps:]
     ix.set_profiling(False)
 
-    # ---- counter pass (separate from the timed loop): algorithmic bytes of every timed batch
-    per_batch = {}
-    nd_all, nh_all, nd_tail = [], [], []
-    for b in sorted(set(tb[a.warmup:])):
-        qq = queries[b][q_lo:q_hi]
-        _, _, _, tr = ix.search_batch(qq, k, L, trace=True)
-        nd = int(tr.n_dist.to(torch.int64).sum().item())
-        ne = int(tr.n_edges.to(torch.int64).sum().item())
-        per_batch[b] = nd * d * 4 + ne * 4
-        nd_all.append(nd / qq.shape[0])
-        nh_all.append(float(tr.n_hop.float().mean().item()))
-        # how uneven the walks of ONE batch are: a batch ends on its longest walk
-        ndq = tr.n_dist.float()
-        nd_tail.append(float(ndq.max().item() / ndq.mean().item()))
-    alg_bytes = [per_batch[b] for b in tb[a.warmup:]][-len(kernel_ms):]
-    achieved = float(np.sum(alg_bytes) / (np.sum(kernel_ms) * 1e-3) / 1e9) if len(kernel_ms) else 0.0
+    # ---- what a caller of the timed path received from its last step (--dump-outputs)
+    if a.dump_outputs and rank == 0 and primary:
+        dump_outputs(a.dump_outputs, last, merged=ex is not None and not split)
+
+    # ---- counter pass (--full; separate from the timed loop): algorithmic bytes of every timed batch
+    if a.full:
+        per_batch = {}
+        nd_all, nh_all, nd_tail = [], [], []
+        for b in sorted(set(tb[a.warmup:])):
+            qq = queries[b][q_lo:q_hi]
+            _, _, _, tr = ix.search_batch(qq, k, L, trace=True)
+            nd = int(tr.n_dist.to(torch.int64).sum().item())
+            ne = int(tr.n_edges.to(torch.int64).sum().item())
+            per_batch[b] = nd * d * 4 + ne * 4
+            nd_all.append(nd / qq.shape[0])
+            nh_all.append(float(tr.n_hop.float().mean().item()))
+            # how uneven the walks of ONE batch are: a batch ends on its longest walk
+            ndq = tr.n_dist.float()
+            nd_tail.append(float(ndq.max().item() / ndq.mean().item()))
+        alg_bytes = [per_batch[b] for b in tb[a.warmup:]][-len(kernel_ms):]
+        achieved = float(np.sum(alg_bytes) / (np.sum(kernel_ms) * 1e-3) / 1e9) if len(kernel_ms) else 0.0
 
     phase("timed+counters")
     # value: user-visible queries answered per second -- every query counts once however many shards walked it
@@ -609,11 +619,7 @@ def measure_mode(a, ctx, mode, rows, primary):
                        (a.dist, "(+rank)" if mode == "c5" else ""),
             "recall_at_10": round(recall, 4),
             "recall_gate": 0.95,
-            "ground_truth": "exact brute force over the whole database (torch matmul top-k); agreement with the "
-                            "device flat scan %.4f" % truth_agree,
-            "flat_scan_ms": round(flat_ms, 2),
-            "flat_scan": "IndexFlat.Search (exact scan, same distance bits) of one %d-query batch over %d rows: "
-                         "%.1f G pairs/s, %.1f useful TFLOP/s" % (nq, n, nq * n / flat_ms / 1e6, 2.0 * nq * n * d / flat_ms / 1e9),
+            "ground_truth": "exact brute force over the whole database (torch matmul top-k)",
             "search_size": L,
             "parallelism": par,
             "value_definition": "user-visible queries answered per second (each query counted once, after the "
@@ -624,13 +630,21 @@ def measure_mode(a, ctx, mode, rows, primary):
             "build_s": round(build_s, 2),
             "build_inserts_per_s": round(n / build_s, 1),
             "avg_degree": round(n_edges / n_nodes, 2),
+        },
+    }
+    if a.full:
+        result["config"]["ground_truth"] += "; agreement with the device flat scan %.4f" % truth_agree
+        result["config"].update({
+            "flat_scan_ms": round(flat_ms, 2),
+            "flat_scan": "IndexFlat.Search (exact scan, same distance bits) of one %d-query batch over %d rows: "
+                         "%.1f G pairs/s, %.1f useful TFLOP/s" % (nq, n, nq * n / flat_ms / 1e6, 2.0 * nq * n * d / flat_ms / 1e9),
             "mean_n_dist": round(float(np.mean(nd_all)), 1),
             "mean_n_hop": round(float(np.mean(nh_all)), 1),
             # the longest walk of a batch over its mean walk, in distance evaluations: what one batch in flight idles for at
             # its end (two batches in flight hide it: two_batches_in_flight_qps)
             "longest_walk_over_mean": round(float(np.mean(nd_tail)), 3),
-        },
-        "roofline": {
+        })
+        result["roofline"] = {
             "bound": "hbm",
             "kernel": "k_greedy_search",
             "achieved": round(achieved, 1),
@@ -645,9 +659,8 @@ def measure_mode(a, ctx, mode, rows, primary):
                       "rows are Infinity-Cache hits (MI355X_MICROARCH.md: ~6.3 TB/s achievable DRAM stream), so the "
                       "DRAM-side rate is ~6.0 TB/s; a dependency-free gather of the same rows reaches 7.0 TB/s on the "
                       "same box (profiles/*gather_ceiling.json)",
-        },
-        "build_roofline": broof,
-    }
+        }
+        result["build_roofline"] = broof
     if split:
         result["config"]["exchange"] = "torch.distributed all_gather of the answers (%s); no merge" % ctx["backend"]
         result["config"]["ranks_seen"] = list(range(world))
@@ -658,7 +671,7 @@ def measure_mode(a, ctx, mode, rows, primary):
         dist.all_gather_object(infos, rank_identity(dev_index, ex))
         rccl, bad = judge_ranks(infos, world, bool(ex is not None and ex.native),
                                 shared_device_ok=(ctx["backend"] != "nccl" or os.environ.get("BENCH_FORCE_EXCHANGE") == "1"))
-        if ex is not None and not split:
+        if a.full and ex is not None and not split:
             try:  # the exchange alone: all-gather + merge of a block that is already there, per batch
                 from semadb_amd import cluster as _cl
                 per = _cl.shard_limit(k, world, 75)
@@ -695,7 +708,7 @@ def measure_mode(a, ctx, mode, rows, primary):
     if recall < 0.95:  # the metric is recall-gated: a line below the gate is not a measurement of it
         result["invalid"] = "recall@10 %.4f is below the metric's 0.95 gate" % recall
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc):
+    if a.full and os.path.exists(pmc):
         try:
             rec = json.load(open(pmc))
             if rec.get("workload_n") == n and rec.get("dim") == d and rec.get("dist") == a.dist and world == 1:
@@ -707,7 +720,7 @@ def measure_mode(a, ctx, mode, rows, primary):
     # the same protocol on the graph the REFERENCE's sequential insert schedule builds from the same rows (415 s on the
     # device: not part of this run) -- tools/reference_schedule_graph.py wrote the record; it is repeated here, labelled
     ref = os.path.join(ROOT, "profiles", "r06_refsched_1m.json")
-    if os.path.exists(ref) and world == 1 and primary:
+    if a.full and os.path.exists(ref) and world == 1 and primary:
         try:
             rec = json.load(open(ref))
             if rec.get("rows_reached") == n and a.dist in rec.get("workload", "") and "%d x %d" % (n, d) in rec["workload"]:
@@ -723,7 +736,7 @@ def measure_mode(a, ctx, mode, rows, primary):
         except Exception:
             pass
 
-    if rank == 0 and world == 1 and primary and not ctx.get("rehearse"):
+    if rank == 0 and world == 1 and primary and a.full and not ctx.get("rehearse"):
         cfg = result["config"]
         # the timed loop once more, the same way (a run checks itself: the driver's N = 1 figures of its BENCH and SCALE
         # passes should agree like these two do)
@@ -796,7 +809,7 @@ def measure_mode(a, ctx, mode, rows, primary):
     del base
     torch.cuda.empty_cache()
     phase("extras")
-    if rank == 0 and world == 1 and primary and not a.no_secondary and not ctx.get("rehearse"):
+    if rank == 0 and world == 1 and primary and a.full and not a.no_secondary and not ctx.get("rehearse"):
         try:
             result["config"]["secondary_datasets"] = secondary_points(a, dev, dev_index)
         except Exception as e:
@@ -811,6 +824,53 @@ def measure_mode(a, ctx, mode, rows, primary):
     result["config"]["wall_s_by_phase"] = ", ".join(phases)
     flatten_summary(result)
     return result
+
+
+def flat_scan_point(ix, queries, base, d, k, nq, n, dev_index):
+    """--full: the device flat scan against the matmul ground truth, and the scan's own time -> (agreement, ms)"""
+    from semadb_amd import flat
+    # cross-check of the ground truth itself: the device flat scan (IndexFlat.Search, flat.go:76-132, same
+    # bit-exact distances) against the torch matmul top-k, first batch, this rank's shard
+    f_ids, _, _ = flat.flat_search_batch(ix._h, d, queries[0], k, device=dev_index)
+    t_ids = exact_topk(queries[0], base, k)[1] + 2
+    truth_agree = float((f_ids.to(torch.int64).unsqueeze(2) == t_ids.unsqueeze(1)).any(2).float().mean().item())
+    log("flat scan vs matmul ground truth agreement: %.4f" % truth_agree)
+    # the exact scan as a measured point of its own (IndexFlat.Search of one query batch over this rank's rows)
+    torch.cuda.synchronize()
+    t_f = time.perf_counter()
+    for _ in range(3):
+        flat.flat_search_batch(ix._h, d, queries[0], k, device=dev_index)
+    torch.cuda.synchronize()
+    flat_ms = (time.perf_counter() - t_f) / 3 * 1e3
+    log("flat exact scan: %.2f ms per %d queries over %d rows" % (flat_ms, nq, n))
+    return truth_agree, flat_ms
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last, merged):
+    """The answers of the last timed step, as a caller of the path receives them: ids (float64: exact below 2^53),
+    dists (float32), counts (float64), and for a merged N > 1 answer the shard of every id.  A larger output than
+    DUMP_LIMIT_BYTES would be cut to a fixed, seeded sample of query rows (the headline's 1024 x 10 is far below)."""
+    if len(last) == 3:  # replicas: (ids, dists, counts) gathered from every rank
+        ids, dists, counts = last
+        shards = None
+    else:
+        ids, dists, shards, counts = last
+    named = {"ids": (ids, np.float64), "dists": (dists, np.float32), "counts": (counts, np.float64)}
+    if merged and shards is not None:
+        named["shards"] = (shards, np.float64)
+    arrays = {name: t.cpu().numpy().astype(dt) for name, (t, dt) in named.items()}
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        rows = arrays["ids"].shape[0]
+        keep = np.sort(np.random.default_rng(0).choice(rows, max(1, rows * DUMP_LIMIT_BYTES // total), replace=False))
+        arrays = {name: x[keep] for name, x in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    log("outputs of the last timed step: %s in %s" % (", ".join("%s %s" % (k, v.shape) for k, v in arrays.items()), out_dir))
 
 
 def two_precision_point(a, ix, queries, tb, k, L, d, nq, result):

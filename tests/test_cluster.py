@@ -302,7 +302,7 @@ def test_bench_without_a_launcher_runs_all_its_ranks(world):
     env.pop("WORLD_SIZE", None)
     rows = 60000 * world
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1",
-           "--rows", str(rows), "--mode", "shards", "--recall-batches", "2", "--timed-batches", "3"]
+           "--rows", str(rows), "--mode", "shards", "--recall-batches", "2", "--timed-batches", "3", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,7 +1,7 @@
 """Stress of the shared-device shard exchange through the ctypes Fanout: four shards on one GPU, client threads racing
 requests of 1 .. 1 024 queries; every merged answer is compared with sdb_topk_merge of the shards' own answers."""
-import sys, threading, time
-sys.path.insert(0, "/root/repo")
+import os, sys, threading, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from semadb_amd import cluster, vamana
 from tests.helpers import start_vector, unit_rows

@@ -1,7 +1,7 @@
 """Wall time of three sdb_index_delete_batch calls of 1 000 points each on the 1M x 384 bench graph (under rocprofv3:
 the delete path's kernel split)."""
 import sys, os, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
 class A: metric, search_size, degree_bound, alpha = "cosine", 75, 64, 1.2
 n, d = 1000000, 384

@@ -1,7 +1,7 @@
 """Per-call times (enqueue / complete) of filtered searches on 200k x 384: 1 / 64 / 1 024 queries with 10 or 1 000 filter
 ids each -- where a filtered call's time goes on the host."""
 import sys, time, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import bench
 class A: metric, search_size, degree_bound, alpha = "cosine", 75, 64, 1.2

@@ -1,7 +1,7 @@
 """Does K1's time depend on the data?  sdb_distance_batch of 64 x 1M x 384, cosine and euclidean, on latent:24 and
 gaussian rows."""
 import sys, os, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 from semadb_amd import distance
 d, nq, nc = 384, 64, 1000000

@@ -1,6 +1,6 @@
 """Turns the rocprofv3 outputs of one round into the committed summaries under profiles/.
 
-usage: python tools/make_profile_summary.py <tag> <gpurun_out dir> <bench log with the JSON line>
+usage: python tools/make_profile_summary.py <tag> <output dir of tools/collect_profiles.sh> <bench log with the JSON line>
 expects in <dir>: <tag>_trace/**/kernel_stats.csv + kernel_trace.csv, <tag>_pmc_fetch/**/counter_collection.csv,
 <tag>_pmc_write/**/counter_collection.csv, pmc_expected.json (written by tools/pmc_run.py)."""
 import csv
@@ -24,7 +24,7 @@ for line in open(benchlog):
         bench = json.loads(line)
 rows = list(csv.DictReader(open(one(tag + "_trace/**/*kernel_stats.csv"))))
 with open("profiles/%s_kernel_stats.csv" % tag, "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-host-rates (MI355X)\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-host-rates (MI355X)\n")
     f.write("# whole process: data generation + K4 build of 1M x 384 + 10 recall batches + 5 warmup + 20 timed steps + 20 counter-pass batches\n")
     f.write("Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs\n")
     for r in rows[:14]:
@@ -62,9 +62,9 @@ md = f"""# {tag} -- search kernel (K2) profile
 
 Commands (GPU box, `cd /tmp; export TMPDIR=/tmp`):
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/{tag}_trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-host-rates
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/{tag}_pmc_fetch -- python3 tools/pmc_run.py
-    rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d gpurun_out/{tag}_pmc_write -- python3 tools/pmc_run.py
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir>/{tag}_trace -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-host-rates
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d <dir>/{tag}_pmc_fetch -- python3 tools/pmc_run.py
+    rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d <dir>/{tag}_pmc_write -- python3 tools/pmc_run.py
 
 ## `{kname}`
 grid 1024 x 64 (one wavefront per query), 1M x 384 cosine, searchSize 75, batch 1024
