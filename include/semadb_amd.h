@@ -271,7 +271,10 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
  *                        distance of a discarded neighbour is never used again).  Ids, distances, visit order and
  *                        counters are the same bits either way.  2: the same, and every discarded neighbour is
  *                        evaluated exactly as well; sdb_index_sketch_stats counts decisions the exact distance
- *                        contradicts (must stay 0).  0: off, the copy is freed.  Off by default. */
+ *                        contradicts (must stay 0).  0: off, the copy is freed.  On (1) by default.  The copy is a
+ *                        cache: it is taken only when the device keeps max(4 GB, a sixteenth of its memory) free
+ *                        afterwards, a table that grows drops it rather than fail, and a device error while building it
+ *                        leaves it off (the write itself succeeds); searches then read float32 rows. */
 #define SDB_TUNE_HUB_MIN 1
 #define SDB_TUNE_HASH_LIMIT 2
 #define SDB_TUNE_NO_HASH 3

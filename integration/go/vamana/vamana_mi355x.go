@@ -90,11 +90,12 @@ func randomUnitVector(d int) []float32 {
 }
 
 // NewIndexVamana (vamana.go:54-81): device index + vector store, filled from the bucket.
-// TwoPrecisionSearch switches SDB_TUNE_SKETCH on for every index created afterwards (a server sets it once from its
+// TwoPrecisionSearch sets SDB_TUNE_SKETCH for every index created afterwards (a server sets it once from its
 // configuration): the device keeps a float16 copy of the rows (+ 50 % of their memory) and a batch search reads a
 // neighbour's float32 row only when its float16 distance does not prove that AddWithLimit discards it
-// (distset.go:184).  Same answers, bit for bit; 1.50 M against 1.07 M queries/s at 1M x 384.  Off like in the library.
-var TwoPrecisionSearch = false
+// (distset.go:184).  Same answers, bit for bit; 1.50 M against 1.07 M queries/s at 1M x 384.  On like in the library;
+// false switches it off explicitly (and frees the copy).
+var TwoPrecisionSearch = true
 
 func NewIndexVamana(name string, params models.IndexVectorVamanaParameters, bucket diskstore.Bucket) (*IndexVamana, error) {
 	mc, ok := metricCode[params.DistanceMetric]
@@ -125,11 +126,13 @@ func NewIndexVamana(name string, params models.IndexVectorVamanaParameters, buck
 		v.Close()
 		return nil, fmt.Errorf("could not setup start node: %w", err)
 	}
-	if TwoPrecisionSearch { // (after the load: the copy is built from the rows that are there, commits keep it current)
-		if rc := C.sdb_index_set_tuning(v.h, C.SDB_TUNE_SKETCH, 1); rc != C.SDB_OK {
-			v.Close()
-			return nil, lastErr("could not switch the two-precision search on", rc)
-		}
+	sketch := C.uint64_t(0) // (after the load: the copy is built from the rows that are there, commits keep it current)
+	if TwoPrecisionSearch {
+		sketch = 1
+	}
+	if rc := C.sdb_index_set_tuning(v.h, C.SDB_TUNE_SKETCH, sketch); rc != C.SDB_OK {
+		v.Close()
+		return nil, lastErr("could not set the two-precision search", rc)
 	}
 	v.batcher = newSearchBatcher(v, 1024, 200*time.Microsecond, 4) // batches in flight: see semadb_host.hpp (2 -> 4: 1.06 -> 1.18 M queries/s)
 	return v, nil

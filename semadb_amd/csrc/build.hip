@@ -1568,6 +1568,12 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     SDB_W_HIP(hipMemcpyAsync(ix->d_bstats + kStRounds, &nr, 8, hipMemcpyHostToDevice, stream));
   }
   if (int rc = check_flags()) return round_failed(rc);
+  if (pairc) {  // the pair cache has served its rounds: returned before the commit asks for the float16 copy (index.h)
+    SDB_W_HIP(hipStreamSynchronize(stream));
+    for (void *&p : cleanup.ptrs)
+      if (p == pairc) (void)hipFree(p), p = nullptr;
+    pairc = nullptr;
+  }
   if (!ix->tx_explicit) {  // the call is its own transaction: publish
     if (int rc = ix->commit(stream)) return round_failed(rc);
     SDB_W_HIP(hipStreamSynchronize(stream));

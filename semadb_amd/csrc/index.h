@@ -139,7 +139,8 @@ struct sdb_index {
   };
   mutable IdMap idmap;
   int ensure_idmap(const View &vw, hipStream_t stream) const;  // view_mu held (shared)
-  bool in_tx = false, tx_explicit = false;
+  std::atomic<bool> in_tx{false};  // read by searches (under the shared view lock) while the writer opens a transaction
+  bool tx_explicit = false;
   bool tx_dirty = false;  // the open transaction has changed the writer's copy or the host tables (sdb_index_abort_write)
   uint32_t tx_n0 = 0;  // rows at the start of the open transaction
   uint32_t tx_dead0 = 0;        // tombstones, largest node id and id-table form at the start of it (rollback)
@@ -160,17 +161,28 @@ struct sdb_index {
   bool tune_no_zero_copy = false;  // A/B and parity tests: host-memory searches stage even page-locked buffers
   // Two-precision hop (SDB_TUNE_SKETCH; search_kernel.h SearchArgs::sketch): a float16 copy of the slab's rows, an
   // optional cache like d_adjcodes.  It describes the rows of the view published as number `sketch_gen`; a search
-  // uses it only while that is the current view, and commit / publish_full rebuild it behind the searches of the old one.
-  uint32_t tune_sketch = 0;  // 0 off, 1 on, 2 on + audit (every discarded neighbour is evaluated exactly as well and checked)
+  // uses it only while that is the current view.  Every path that publishes rows (load, commit, publish_full,
+  // rollback, compact) brings it up to date behind the searches of the old view, and reserve() carries it across
+  // table growth.  Pointers, capacity, maxima and generation change under the exclusive view_mu only (searches read
+  // them once under the shared lock); the conversion kernel runs outside it, serialised against the knob by sketch_mu.
+  // Best-effort: no room for it (build_sketch's headroom rule) or a device error while building it leaves it off and
+  // the walk reads float32 rows -- never a failed write.
+  uint32_t tune_sketch = 1;  // 0 off (the copy is freed), 1 on (default), 2 on + audit (every discarded neighbour is evaluated exactly as well and checked)
   uint16_t *d_sketch = nullptr;
   float *d_sketch_norm = nullptr;  // [sketch_cap] ||y16||^2 per row (the euclidean form of the first stage)
   uint32_t sketch_cap = 0;   // rows d_sketch has room for
-  std::atomic<uint64_t> sketch_gen{0};  // view_gen the copy was built for (0: none); written last by build_sketch, read by searches under the shared view lock
+  std::atomic<uint64_t> sketch_gen{0};  // view_gen the copy was built for (0: none); written under the exclusive view_mu
   float sk_emax = 0.0f, sk_ymax = 0.0f;
   unsigned long long *d_sk_counters = nullptr;  // [0] neighbours discarded on their float16 distance, [1] contradicted (audit)
-  bool sketch_supported() const;               // cosine / dot rows of whole 32-float blocks, one of the walk's register layouts
-  int build_sketch(hipStream_t stream, uint32_t from = 0);  // (re)build for the rows as they are (from > 0: only the rows from there on); failure to allocate leaves it off
-  void drop_sketch();
+  std::mutex sketch_mu;  // held by build_sketch on the commit path (view_mu released) and by the knob: lock order sketch_mu, view_mu
+  // plain rows of whole 32-float blocks in one of the walk's register layouts (ng 1, 2, 3, 4, 6), any metric, no quantizer
+  bool sketch_supported() const;
+  bool sketch_current() const { return d_sketch && sketch_gen == view_gen; }  // describes the current view's rows
+  static bool sketch_room(size_t bytes);  // the device keeps max(4 GB, total / 16) free after `bytes` more (a cache's rule, build.hip pairc)
+  // (Re)build for the rows as they are (from > 0: only the rows from there on).  `locked`: the caller holds view_mu
+  // exclusively.  Never fails: no room or a device error drops the copy.  Off or unsupported: the copy is freed.
+  void build_sketch(hipStream_t stream, uint32_t from, bool locked);
+  void drop_sketch();  // view_mu held exclusively (or no search can run); waits for the walks that may read it
   bool tune_no_defer = false;  // A/B and parity tests: every back-edge re-prune runs in k_backedges (BuildArgs::def_*)
   uint32_t tune_pq_narrow = 0;  // 1: quantized searches never take a multi-wave walk (k_greedy_search_pqw, k_greedy_search_pq2): A/B and parity tests
   bool tune_no_mfma = false;  // exact scan of dot/cosine rows on the packed-FMA kernel instead of the matrix cores

@@ -680,23 +680,62 @@ int sdb_index::reserve(uint32_t rows) {
   uint32_t *nadj = nullptr, *nradj = nullptr, *ndeg = nullptr, *nclean = nullptr, *ndc = nullptr;
   uint64_t *nids = nullptr, *nrids = nullptr;
   uint8_t *ndirty = nullptr, *ncodes = nullptr;
-  SDB_TRY(fresh.get((void **)&nslab, (size_t)ncap * lay.ld * sizeof(float)));
-  SDB_TRY(fresh.get((void **)&nadj, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
-  SDB_TRY(fresh.get((void **)&nradj, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
-  SDB_TRY(fresh.get((void **)&ndeg, (size_t)ncap * sizeof(uint32_t)));
-  SDB_TRY(fresh.get((void **)&nclean, (size_t)ncap * sizeof(uint32_t)));
-  SDB_TRY(fresh.get((void **)&nids, (size_t)ncap * sizeof(uint64_t)));
-  SDB_TRY(fresh.get((void **)&nrids, (size_t)ncap * sizeof(uint64_t)));
-  SDB_TRY(fresh.get((void **)&ndirty, (size_t)ncap));
-  SDB_TRY(fresh.get((void **)&nad, (size_t)ncap * kAdjStride * sizeof(float)));  // edge-distance cache of the write path (index.h)
-  SDB_TRY(fresh.get((void **)&ndc, (size_t)ncap * sizeof(uint32_t)));
-  if (pq) SDB_TRY(fresh.get((void **)&ncodes, (size_t)ncap * pq->M));  // the code rows of a quantized store grow with it
+  std::unique_lock<std::mutex> sg(sketch_mu);  // the knob waits until the float16 copy has followed the growth
+  auto get_required = [&]() -> int {
+    SDB_TRY(fresh.get((void **)&nslab, (size_t)ncap * lay.ld * sizeof(float)));
+    SDB_TRY(fresh.get((void **)&nadj, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
+    SDB_TRY(fresh.get((void **)&nradj, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
+    SDB_TRY(fresh.get((void **)&ndeg, (size_t)ncap * sizeof(uint32_t)));
+    SDB_TRY(fresh.get((void **)&nclean, (size_t)ncap * sizeof(uint32_t)));
+    SDB_TRY(fresh.get((void **)&nids, (size_t)ncap * sizeof(uint64_t)));
+    SDB_TRY(fresh.get((void **)&nrids, (size_t)ncap * sizeof(uint64_t)));
+    SDB_TRY(fresh.get((void **)&ndirty, (size_t)ncap));
+    SDB_TRY(fresh.get((void **)&nad, (size_t)ncap * kAdjStride * sizeof(float)));  // edge-distance cache of the write path (index.h)
+    SDB_TRY(fresh.get((void **)&ndc, (size_t)ncap * sizeof(uint32_t)));
+    if (pq) SDB_TRY(fresh.get((void **)&ncodes, (size_t)ncap * pq->M));  // the code rows of a quantized store grow with it
+    return SDB_OK;
+  };
+  if (int rc = get_required()) {
+    if (!d_sketch) return rc;
+    // a required buffer never goes without for the float16 copy's sake (a cache): drop it and try once more
+    (void)hipGetLastError();
+    for (void *x : fresh.p)
+      if (x) (void)hipFree(x);
+    fresh.p.clear();
+    {
+      std::unique_lock<sdb::ViewMutex> wl(view_mu);
+      drop_sketch();
+    }
+    SDB_TRY(get_required());
+  }
   uint8_t *nacw = nullptr, *nacr = nullptr;  // ... and the neighbours' code rows behind both adjacency copies
   const bool had_ac = has_adjcodes();
   size_t ac_row = had_ac ? (size_t)kAdjStride * pq->M : 0;
   // (2 x 64 M bytes per row: 41 GB at 10M rows and M = 32, more than the vectors of d = 768.  A table that grows past
   // the room for them drops them instead of failing the insert -- alloc_adjcodes treats them as optional the same way)
   if (ac_row && !fresh.get_pair_if_room((void **)&nacw, (void **)&nacr, (size_t)ncap * ac_row)) ac_row = 0;
+  // the float16 copy grows with the slab, best-effort under the headroom rule: rows do not move, so it stays current and
+  // the next commit converts only the rows it appends (without room the copy keeps covering the rows it has).  Chosen
+  // order: a table that already serves from the copy keeps it through growth, so on a device near capacity a bulk
+  // insert_batch into a grown table may find no headroom left for its pair cache (build.hip pairc) and build without
+  // it -- slower, same graph -- rather than have every search fall back to float32 rows.
+  const bool sk_keep = sketch_current();
+  uint16_t *nsk = nullptr;
+  float *nskn = nullptr;
+  if (sk_keep && sketch_cap < ncap) {
+    const size_t rows_b = (size_t)ncap * lay.ld * sizeof(uint16_t), norm_b = (size_t)ncap * sizeof(float);
+    const uint32_t have = std::min(n, sketch_cap);
+    if (!sketch_room(rows_b + norm_b) || hipMalloc(&nsk, rows_b) != hipSuccess || hipMalloc(&nskn, norm_b) != hipSuccess ||
+        (have && (hipMemcpy(nsk, d_sketch, (size_t)have * lay.ld * sizeof(uint16_t), hipMemcpyDeviceToDevice) != hipSuccess ||
+                  hipMemcpy(nskn, d_sketch_norm, (size_t)have * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess))) {
+      (void)hipGetLastError();
+      if (nsk) (void)hipFree(nsk);
+      if (nskn) (void)hipFree(nskn);
+      nsk = nullptr, nskn = nullptr;
+    } else {
+      fresh.p.push_back(nsk), fresh.p.push_back(nskn);  // returned with the rest if a step below fails
+    }
+  }
   // the old buffers are freed below: nothing may still be walking them (searches run on streams of their own)
   if (cap) SDB_HIP(hipDeviceSynchronize());
   SDB_HIP(hipMemset(nadj, 0xFF, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
@@ -739,6 +778,11 @@ int sdb_index::reserve(uint32_t rows) {
     cap = ncap;
     view.adj = r_adj, view.ids = r_ids, view.adj_codes = r_adjcodes;
     view_gen++;
+    if (nsk) {
+      (void)hipFree(d_sketch), (void)hipFree(d_sketch_norm);
+      d_sketch = nsk, d_sketch_norm = nskn, sketch_cap = ncap;
+    }
+    if (sk_keep) sketch_gen = view_gen;
   }
   return SDB_OK;
 }
@@ -862,7 +906,17 @@ bool sdb_index::sketch_supported() const {
   return lay.ng == 1 || lay.ng == 2 || lay.ng == 3 || lay.ng == 4 || lay.ng == 6;
 }
 
+bool sdb_index::sketch_room(size_t bytes) {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return free_b >= bytes + std::max<size_t>((size_t)4 << 30, total_b / 16);
+}
+
 void sdb_index::drop_sketch() {
+  if (d_sketch || d_sketch_norm) (void)hipDeviceSynchronize();  // walks of earlier views may still read it
   if (d_sketch) (void)hipFree(d_sketch);
   if (d_sketch_norm) (void)hipFree(d_sketch_norm);
   d_sketch = nullptr, d_sketch_norm = nullptr, sketch_cap = 0, sketch_gen = 0;
@@ -870,44 +924,67 @@ void sdb_index::drop_sketch() {
 
 // `from` > 0: the copy is current for rows [0, from) -- a Vamana table never rewrites a committed row, it appends
 // (updates are delete + insert, vamana.go:170-251) -- and only the rows behind them are converted; the two maxima
-// carry on from their values (they stay upper bounds when rows are deleted).
-int sdb_index::build_sketch(hipStream_t stream, uint32_t from) {
-  const bool carry = from > 0 && from <= n && d_sketch && sketch_cap >= cap && sketch_gen != 0;
+// carry on from their values (they stay upper bounds when rows are deleted).  Pointers, capacity, maxima and the
+// generation change under the exclusive view lock; the conversion runs outside it when the caller does not hold it
+// (commit: searches of the new view go on reading float32 rows until sketch_gen names it).  Rows below `from` are
+// not written, so the walks of the previous view that still read them are undisturbed.
+void sdb_index::build_sketch(hipStream_t stream, uint32_t from, bool locked) {
+  std::unique_lock<std::mutex> sg(sketch_mu, std::defer_lock);
+  std::unique_lock<sdb::ViewMutex> wl(view_mu, std::defer_lock);
+  if (!locked) sg.lock(), wl.lock();
+  if (!tune_sketch || !sketch_supported()) {  // off, or a table the walk cannot take it for: no memory held for it
+    drop_sketch();
+    return;
+  }
+  const bool carry = from > 0 && from <= n && d_sketch && sketch_cap >= n && sketch_gen != 0;
   if (!carry) from = 0;
   sketch_gen = 0;
-  if (!tune_sketch || !sketch_supported() || n == 0) return SDB_OK;
-  if (sketch_cap < cap) {
+  if (n == 0) return;
+  if (sketch_cap < n) {
     drop_sketch();
-    if (hipMalloc(&d_sketch, (size_t)cap * lay.ld * sizeof(uint16_t)) != hipSuccess ||
-        hipMalloc(&d_sketch_norm, (size_t)cap * sizeof(float)) != hipSuccess) {  // a cache: without room for it the walk reads float32 rows
-      (void)hipGetLastError();
+    const size_t rows = (size_t)cap * lay.ld * sizeof(uint16_t), norms = (size_t)cap * sizeof(float);
+    // a cache: without room for it (the rule of build.hip's pair cache) the walk reads float32 rows
+    if (!sketch_room(rows + norms) || hipMalloc(&d_sketch, rows) != hipSuccess || hipMalloc(&d_sketch_norm, norms) != hipSuccess) {
+      (void)hipGetLastError();  // (a failed hipMalloc of this cache)
       drop_sketch();
-      return SDB_OK;
+      return;
     }
     sketch_cap = cap;
   }
   if (!d_sk_counters) {
-    if (hipMalloc(&d_sk_counters, 4 * sizeof(unsigned long long)) != hipSuccess) {  // (the copy is optional: so is this)
-      (void)hipGetLastError();
+    if (hipMalloc(&d_sk_counters, 4 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(d_sk_counters, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {  // (the copy is optional: so is this)
+      (void)hipGetLastError();  // (a failed allocation or memset of this cache)
+      if (d_sk_counters) (void)hipFree(d_sk_counters);
       d_sk_counters = nullptr;
       drop_sketch();
-      return SDB_OK;
+      return;
     }
-    SDB_HIP(hipMemset(d_sk_counters, 0, 4 * sizeof(unsigned long long)));
   }
+  uint16_t *const sk = d_sketch;
+  float *const sk_norm = d_sketch_norm;
   uint32_t *stats = reinterpret_cast<uint32_t *>(d_sk_counters + 2);
   uint32_t h[2] = {0, 0};
   if (from) memcpy(&h[0], &sk_emax, 4), memcpy(&h[1], &sk_ymax, 4);
-  SDB_HIP(hipMemcpyAsync(stats, h, 8, hipMemcpyHostToDevice, stream));
-  if (n > from)
-    hipLaunchKernelGGL(sdb::k_sketch_rows, dim3((n - from + 3) / 4), dim3(256), 0, stream, d_slab + (size_t)from * lay.ld,
-                       d_sketch + (size_t)from * lay.ld, d_sketch_norm + from, n - from, lay.ld, stats);
-  SDB_HIP(hipGetLastError());
-  SDB_HIP(hipMemcpyAsync(h, stats, 8, hipMemcpyDeviceToHost, stream));
-  SDB_HIP(hipStreamSynchronize(stream));
+  const uint32_t rows = n, ld = lay.ld;
+  const float *slab = d_slab;
+  if (!locked) wl.unlock();  // (sketch_mu stays held: the knob cannot free the copy under the kernel)
+  bool ok = hipMemcpyAsync(stats, h, 8, hipMemcpyHostToDevice, stream) == hipSuccess;
+  if (ok && rows > from) {
+    hipLaunchKernelGGL(sdb::k_sketch_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
+                       sk + (size_t)from * ld, sk_norm + from, rows - from, ld, stats);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  ok = ok && hipMemcpyAsync(h, stats, 8, hipMemcpyDeviceToHost, stream) == hipSuccess;
+  ok = hipStreamSynchronize(stream) == hipSuccess && ok;
+  if (!locked) wl.lock();
+  if (!ok) {  // best-effort: the write this follows has been published; its searches read float32 rows
+    (void)hipGetLastError();
+    drop_sketch();
+    return;
+  }
   memcpy(&sk_emax, &h[0], 4), memcpy(&sk_ymax, &h[1], 4);
   sketch_gen = view_gen;
-  return SDB_OK;
 }
 
 int sdb_index::ensure_idmap(const View &vw, hipStream_t stream) const {
@@ -980,7 +1057,7 @@ int sdb_index::rebuild_adjcodes(hipStream_t stream) {
 
 int sdb_index::commit(hipStream_t stream) {
   if (!in_tx) return SDB_OK;
-  const bool sk_current = d_sketch && sketch_gen == view_gen && sketch_cap >= cap;  // the float16 copy describes the rows below tx_n0
+  const bool sk_current = sketch_current();  // the float16 copy describes the rows below tx_n0
   const uint32_t need = (uint32_t)((h_start_ext.size() + 63) / 64 * 64);
   const uint32_t ac_bytes = has_adjcodes() ? kAdjStride * pq->M : 0;
   if (ac_bytes && n) {
@@ -1029,8 +1106,8 @@ int sdb_index::commit(hipStream_t stream) {
     SDB_HIP(hipMemcpyAsync(d_start_ext, r_start_ext, (size_t)need * 4, hipMemcpyDeviceToDevice, stream));
   }
   // the float16 copy follows: on `stream`, which has waited for the searches of the old view (above); searches of the
-  // new one read float32 rows until sketch_gen says the copy is theirs
-  if (tune_sketch) SDB_TRY(build_sketch(stream, sk_current && start_slot >= 0 ? tx_n0 : 0));
+  // new one read float32 rows until sketch_gen says the copy is theirs.  Best-effort: the write is published already.
+  build_sketch(stream, sk_current && start_slot >= 0 ? tx_n0 : 0, false);
   return SDB_OK;
 }
 
@@ -1081,7 +1158,8 @@ int sdb_index::rollback() {
   }
   tx_deleted.clear();
   in_tx = false, tx_explicit = false, tx_dirty = false;
-  if (tune_sketch) SDB_TRY(build_sketch(nullptr));  // (exclusive lock held, device idle)
+  // the committed rows are where they were: a current copy still describes them (exclusive lock held, device idle)
+  if (!sketch_current() || sketch_cap < n) build_sketch(nullptr, 0, true);
   return SDB_OK;
 }
 
@@ -1114,10 +1192,8 @@ int sdb_index::publish_full() {
   view_gen++;
   tx_deleted.clear();
   in_tx = false, tx_explicit = false, tx_dirty = false;
-  if (tune_sketch) {
-    SDB_HIP(hipDeviceSynchronize());  // searches that slipped in between the first wait and the lock
-    SDB_TRY(build_sketch(nullptr));
-  }
+  SDB_HIP(hipDeviceSynchronize());  // searches that slipped in between the first wait and the lock
+  build_sketch(nullptr, 0, true);  // (best-effort: the view is published)
   return SDB_OK;
 }
 
@@ -1844,10 +1920,15 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
   a.wide_hash = ix->tune_wide_hash ? 1u : 0u, a.hash16_probes = ix->tune_hash16_probes;
   a.pq_narrow = ix->tune_pq_narrow;
   a.wide_mode = ix->tune_wide_walk;
-  // two-precision hop: only with the float16 copy of exactly this view's rows, outside a write transaction
-  if (ix->tune_sketch && ix->d_sketch && ix->sketch_gen == ix->view_gen && !ix->in_tx && !filtered)
-    a.sketch = ix->d_sketch, a.sketch_norm = ix->d_sketch_norm, a.sk_emax = ix->sk_emax, a.sk_ymax = ix->sk_ymax, a.sk_audit = ix->tune_sketch == 2 ? 1u : 0u,
-    a.sk_counters = ix->d_sk_counters;
+  // two-precision hop: only with the float16 copy of exactly this view's rows, outside a write transaction.  Every
+  // field is read once, under the shared lock the writer's changes to them exclude.
+  {
+    const uint32_t knob = ix->tune_sketch;
+    const uint16_t *sk = ix->d_sketch;
+    if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx && !filtered)
+      a.sketch = sk, a.sketch_norm = ix->d_sketch_norm, a.sk_emax = ix->sk_emax, a.sk_ymax = ix->sk_ymax,
+      a.sk_audit = knob == 2 ? 1u : 0u, a.sk_counters = ix->d_sk_counters;
+  }
 
   const uint32_t vcap = trace ? trace->visit_cap : 0;
   auto launch = [&]() -> int {
@@ -2027,6 +2108,7 @@ int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
     case SDB_TUNE_SKETCH: {
       if (value > 2) return fail(SDB_ERR_INVALID, "sketch: 0 = off, 1 = on, 2 = on with audit");
       DeviceGuard dg(ix->P.device);
+      std::lock_guard<std::mutex> sg(ix->sketch_mu);  // a commit converting rows on another thread finishes first
       std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
       SDB_HIP(hipDeviceSynchronize());  // walks that read the copy
       ix->tune_sketch = (uint32_t)value;
@@ -2035,7 +2117,8 @@ int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
         return SDB_OK;
       }
       if (ix->d_sk_counters) SDB_HIP(hipMemset(ix->d_sk_counters, 0, 2 * sizeof(unsigned long long)));
-      return ix->in_tx ? SDB_OK : ix->build_sketch(nullptr);  // inside a transaction: its commit builds it
+      if (!ix->in_tx && !ix->sketch_current()) ix->build_sketch(nullptr, 0, true);  // inside a transaction: its commit builds it
+      return SDB_OK;
     }
     case SDB_TUNE_NO_DEFER:
       ix->tune_no_defer = value != 0;
@@ -2061,7 +2144,7 @@ int sdb_index_sketch_stats(sdb_index *ix, uint64_t out[3]) try {
     SDB_HIP(hipMemcpy(h, ix->d_sk_counters, sizeof(h), hipMemcpyDeviceToHost));
     out[0] = h[0], out[1] = h[1];
   }
-  out[2] = (ix->tune_sketch && ix->d_sketch && ix->sketch_gen == ix->view_gen && !ix->in_tx) ? 1 : 0;
+  out[2] = (ix->tune_sketch && ix->sketch_current() && !ix->in_tx) ? 1 : 0;
   return SDB_OK;
 }
 SDB_API_CATCH("sdb_index_sketch_stats")
@@ -2348,7 +2431,7 @@ int sdb_index_compact(sdb_index *ix) try {
   ix->view.adj_codes = ix->r_adjcodes;
   ix->view_gen++;
   (void)hipDeviceSynchronize();
-  if (ix->tune_sketch) (void)ix->build_sketch(nullptr);  // rows have moved (a stale copy is never used: sketch_gen)
+  ix->build_sketch(nullptr, 0, true);  // rows have moved (a stale copy is never used: sketch_gen); best-effort
   return SDB_OK;
 }
 SDB_API_CATCH("sdb_index_compact")
@@ -2484,6 +2567,7 @@ extern "C" int sdb_index_attach_pq(sdb_index *ix, const sdb_pq *pq, void *stream
   if (ix->d_codes) (void)hipFree(ix->d_codes);
   ix->d_codes = ncodes;
   ix->pq = pq;
+  ix->drop_sketch();  // a quantized walk has no use for the float16 copy (sketch_supported)
   // the neighbours' code rows behind the adjacency rows, for the new codes (M <= 32; index.h d_adjcodes)
   SDB_TRY(ix->alloc_adjcodes());
   SDB_TRY(ix->rebuild_adjcodes(stream));

@@ -315,7 +315,8 @@ struct PlainDist {
     // (both halves of the wave hold the same query: the sum over one half's 32 lanes)
     e2 = rlf(asm_reduce(e2, 0.0f, lane), 0), n2 = rlf(asm_reduce(n2, 0.0f, lane), 0);
     const float qerr = __builtin_sqrtf(e2) * 1.0001f, qn = __builtin_sqrtf(n2) * 1.0001f;
-    sk_eps = (qerr * a.sk_ymax + qn * a.sk_emax + 2e-5f * qn * (a.sk_ymax + a.sk_emax)) * 1.0001f;
+    const SearchArgs &c = cold_args(a);  // (what only the hop reads: through the opaque view, not parked in SGPRs)
+    sk_eps = (qerr * c.sk_ymax + qn * c.sk_emax + 2e-5f * qn * (c.sk_ymax + c.sk_emax)) * 1.0001f;
     if constexpr (L2) {
       float hh = 0.0f;
 #pragma unroll
@@ -324,7 +325,7 @@ struct PlainDist {
         hh = __builtin_fmaf(h0, h0, hh), hh = __builtin_fmaf(h1, h1, hh), hh = __builtin_fmaf(h2, h2, hh), hh = __builtin_fmaf(h3, h3, hh);
       }
       sk_qq = rlf(asm_reduce(hh, 0.0f, lane), 0);
-      sk_delta = (qerr + a.sk_emax) * 1.0001f;
+      sk_delta = (qerr + c.sk_emax) * 1.0001f;
     }
   }
 
@@ -353,7 +354,7 @@ struct PlainDist {
   // float16 dot products of the pending rows by rank, two rows per wave instruction like rows_range
   __device__ __forceinline__ void sketch_range(const SearchArgs &a, const uint32_t *s_slot, float *s_res, int cnt, int lane) {
     const int L = lane & 31, half = lane >> 5;
-    const char *baseL = reinterpret_cast<const char *>(a.sketch) + L * 8;
+    const char *baseL = reinterpret_cast<const char *>(cold_args(a).sketch) + L * 8;
     const uint32_t row_bytes = a.ld * 2u;
     for (int c0 = 0; c0 < cnt; c0 += 2 * US) {
       const int m = cnt - c0 < 2 * US ? cnt - c0 : 2 * US;
@@ -433,7 +434,7 @@ struct PlainDist {
     const bool mine = (pend >> lane) & 1ull;
     float yy_me = 0.0f;
     if constexpr (L2)
-      if (mine) yy_me = a.sketch_norm[nb];  // (in flight while the rows are summed)
+      if (mine) yy_me = cold_args(a).sketch_norm[nb];  // (in flight while the rows are summed)
     const uint32_t rank =
         __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
     uint32_t *s_slot = hs;
@@ -494,6 +495,14 @@ struct PlainDist {
     return metric_finish(rlf(res[0], 0), a.metric);
   }
 
+  // Whether a hop asks for its float16 rows ahead: with the array full.  The walk is launched only with the copy
+  // (index.hip launch_plain), so the pointer need not be tested -- and untested, the compiler sees that sketch_keep's
+  // compacting path is never taken with the rows asked for ahead: 87 -> 14 spilled SGPRs at NG = 3 (cosine / dot).  The
+  // euclidean walk keeps the test (through the opaque view): untested, this compiler spills 4 VGPRs there; tested, none.
+  __device__ __forceinline__ bool sketch_go(const SearchArgs &a, bool full) const {
+    if constexpr (L2) return full && cold_args(a).sketch != nullptr;
+    return full;
+  }
   __device__ __forceinline__ void prefetch(const SearchArgs &a, uint32_t nb, bool valid) {  // float32 rows are fetched in hop()
     if constexpr (kSketchAhead) {
       sk_loaded = false;
@@ -501,10 +510,11 @@ struct PlainDist {
       const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
       const int L = lane & 31;
       const bool hi = lane >= 32;
-      const char *baseL = reinterpret_cast<const char *>(a.sketch) + L * 8;
+      // (the copy's addresses through the opaque view at each use: one scalar load, where arguments that live through
+      // the walk would hold SGPR pairs spilled into VGPR lanes -- tools/kernel_table.py)
+      const char *baseL = reinterpret_cast<const char *>(cold_args(a).sketch) + L * 8;
       const uint32_t row_bytes = a.ld * 2u;
       const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
-      if constexpr (L2) sk_yy = a.sketch_norm[safe];
 #pragma unroll
       for (int u = 0; u < 32; u++) {
         const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
@@ -512,6 +522,7 @@ struct PlainDist {
 #pragma unroll
         for (int g = 0; g < NG; g++) sky[u][g] = *reinterpret_cast<const uint2 *>(r + g * 256);
       }
+      if constexpr (L2) sk_yy = cold_args(a).sketch_norm[safe];
       sk_loaded = true;
     }
   }
@@ -2022,7 +2033,7 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
       if (!Dist::kSpeculate) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // charge the adjacency round trip to st_adj
 #endif
       SDB_STAMP(st_adj)
-      if constexpr (sketch_policy<Dist>::value) dist.sk_go = len == cap && a.sketch != nullptr;
+      if constexpr (sketch_policy<Dist>::value) dist.sk_go = dist.sketch_go(a, len == cap);
       dist.prefetch(a, nb, valid);
       // CheckAndVisit distset.go:174 -- marks before any distance test
       bool isnew;
@@ -2040,10 +2051,11 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
             const float tail_d = list_tail(cd, cap);
             uint64_t out = 0;
             const uint64_t keep = dist.sketch_keep(a, nb, pend, lane, tail_d, out);
-            if (a.sk_audit) {  // (rare path: counted at once, not carried in a register through the walk)
+            if (cold_args(a).sk_audit) {  // (rare path: counted at once, not carried in a register through the walk)
               const float dx = dist.hop(a, nb, pend, lane);
               const uint64_t bad = __ballot(((out >> lane) & 1ull) && !(dx > tail_d));
-              if (bad && lane == 0 && a.sk_counters) atomicAdd(a.sk_counters + 1, (unsigned long long)__popcll(bad));
+              unsigned long long *cnt = cold_args(a).sk_counters;
+              if (bad && lane == 0 && cnt) atomicAdd(cnt + 1, (unsigned long long)__popcll(bad));
             }
             n_sk_out += (uint32_t)__popcll(out);
             pend = keep;

@@ -769,6 +769,7 @@ class IndexVamana {
   void setFitSeed(uint64_t s) { fit_seed_ = s; }
   // SDB_TUNE_SKETCH (include/semadb_amd.h): batch searches of plain tables read a float16 copy of the rows first
   // and a neighbour's float32 row only when AddWithLimit may keep it -- same answers, + 50 % of the rows' memory.
+  // On by default in the library; setTwoPrecisionSearch(false) is the opt-out and frees the copy.
   // (The Go twin is the package variable TwoPrecisionSearch, integration/go/vamana/vamana_mi355x.go.)
   Error setTwoPrecisionSearch(bool on) {
     const int rc = sdb_index_set_tuning(h_, SDB_TUNE_SKETCH, on ? 1 : 0);

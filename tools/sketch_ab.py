@@ -12,6 +12,7 @@ base = bench.gen_rows(n, d, 20250620, dist, "cuda:0")
 q = bench.gen_rows(12 * 1024, d, 20250621, dist, "cuda:0").view(12, 1024, d)
 ix = vamana.NewIndexVamana("ab", vamana.IndexVectorVamanaParameters(d, os.environ.get("METRIC", "cosine"), 75, 64, 1.2), capacity=n + 1)
 ix.set_start(bench.start_vector(d))
+ix.set_tuning("sketch", 0)  # the "default" leg is the float32 walk (the copy is on by default)
 ix.insert_batch(None, base)
 out = {"rows": n, "dim": d, "dist": dist}
 
