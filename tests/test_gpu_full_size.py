@@ -181,11 +181,29 @@ def test_c2_oracle_walks_the_same_path(c2, oracle):
     g_ids, g_d = g_ids.cpu().numpy().view(np.uint64), g_d.cpu().numpy()
     vis = tr.visit_ids.cpu().numpy().view(np.uint64)
     qh = q.cpu().numpy()
-    for i in range(qh.shape[0]):
-        o_ids, o_d, o_vis, o_tr = o.search(qh[i], K, L)
+    walks = [o.search(qh[i], K, L) for i in range(qh.shape[0])]
+    for i, (o_ids, o_d, o_vis, o_tr) in enumerate(walks):
         assert np.array_equal(g_ids[i], o_ids) and np.array_equal(bits(g_d[i]), bits(o_d))
         assert int(tr.n_dist[i]) == o_tr.n_dist and int(tr.n_hop[i]) == o_tr.n_hop
         assert np.array_equal(vis[i, :o_tr.n_hop], o_vis), "query %d visit order" % i
+    # A call of 96 queries runs on the many-waves-per-query kernel (index.hip wide_walk()).  The same queries on the
+    # one-wave-per-query walk, the kernel every large batch takes, with its two-precision hop over full rows (R = 64):
+    discarded = c2.ix.sketch_stats()[0]
+    c2.ix.set_tuning("wide_walk", 1)
+    try:
+        g_ids, g_d, g_c, tr = c2.ix.search_batch(q, K, L, trace=True, visit_cap=512)
+        torch.cuda.synchronize()
+        stats = c2.ix.sketch_stats()
+    finally:
+        c2.ix.set_tuning("wide_walk", 0)
+    assert stats[2], "the float16 copy is not in use"
+    assert stats[0] - discarded > 0, "the one-wave walk discarded no neighbour on its float16 distance"
+    g_ids, g_d = g_ids.cpu().numpy().view(np.uint64), g_d.cpu().numpy()
+    vis = tr.visit_ids.cpu().numpy().view(np.uint64)
+    for i, (o_ids, o_d, o_vis, o_tr) in enumerate(walks):
+        assert np.array_equal(g_ids[i], o_ids) and np.array_equal(bits(g_d[i]), bits(o_d)), "query %d, one-wave walk" % i
+        assert int(tr.n_dist[i]) == o_tr.n_dist and int(tr.n_hop[i]) == o_tr.n_hop, "query %d, one-wave walk" % i
+        assert np.array_equal(vis[i, :o_tr.n_hop], o_vis), "query %d visit order, one-wave walk" % i
 
 
 def test_c5_two_shards_merge(c2, oracle):
