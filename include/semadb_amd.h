@@ -264,11 +264,14 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
  *   SDB_TUNE_NO_ZERO_COPY  != 0: a host-memory search stages queries and results through device buffers even when the
  *                        caller's buffers are page-locked (sdb_host_alloc) and the kernel could read / write them in
  *                        place (A/B and parity tests)
- *   SDB_TUNE_SKETCH      1: two-precision hop for batch searches of plain tables, any metric (rows of whole 32-float blocks,
- *                        up to 768 floats; no quantizer, no filter): the index keeps a float16 copy of its rows (+ 50 %
+ *   SDB_TUNE_SKETCH      1: two-precision hop for batch searches of plain tables, any metric (rows of whole 32-float
+ *                        blocks, up to 768 floats; no quantizer; filtered calls with SDB_TUNE_SKETCH_FILTERED): the index keeps a float16 copy of its rows (+ 50 %
  *                        of their memory; a commit converts the rows it appended) and a hop reads a new neighbour's float32 row only
  *                        when its float16 distance does not PROVE that AddWithLimit discards it (distset.go:184: the
- *                        distance of a discarded neighbour is never used again).  Ids, distances, visit order and
+ *                        distance of a discarded neighbour is never used again).  A filtered walk's array is not
+ *                        sorted (its seeds are appended), so there the proof is against the largest of the array's last
+ *                        min(k, searchSize) distances as a row with k new neighbours is met, not against its last one.
+ *                        Ids, distances, visit order and
  *                        counters are the same bits either way.  2: the same, and every discarded neighbour is
  *                        evaluated exactly as well; sdb_index_sketch_stats counts decisions the exact distance
  *                        contradicts (must stay 0).  0: off, the copy is freed.  On (1) by default.  The copy is a
@@ -288,8 +291,13 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
 #define SDB_TUNE_NO_DEFER 11
 #define SDB_TUNE_NO_ZERO_COPY 12
 #define SDB_TUNE_SKETCH 13
+/* != 0: filtered batch searches (id lists and bitmaps, searchSize <= 128) take SDB_TUNE_SKETCH's hop too, with the proof
+ * against the largest of the array's last min(k, searchSize) distances.  Same answers, bit for bit.  Off by default:
+ * a filtered walk discards fewer neighbours than a plain one, and its speed against the float32 walk has not been
+ * measured on the full-size shape (tools/bench_filter.py --sketch measures it). */
+#define SDB_TUNE_SKETCH_FILTERED 14
 int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value);
-/* SDB_TUNE_SKETCH's counters since the knob was last set: out[0] = neighbours discarded on their float16 distance,
+/* SDB_TUNE_SKETCH's counters since the knob was last set, filtered calls (SDB_TUNE_SKETCH_FILTERED) included: out[0] = neighbours discarded on their float16 distance,
  * out[1] = of those, the ones whose exact distance would have been kept (audit mode only; a non-zero value is a bug),
  * out[2] = 1 when searches currently use the float16 copy (it exists and describes the committed rows), else 0. */
 int sdb_index_sketch_stats(sdb_index *ix, uint64_t out[3]);

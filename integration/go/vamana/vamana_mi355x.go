@@ -91,7 +91,7 @@ func randomUnitVector(d int) []float32 {
 
 // NewIndexVamana (vamana.go:54-81): device index + vector store, filled from the bucket.
 // TwoPrecisionSearch sets SDB_TUNE_SKETCH for every index created afterwards (a server sets it once from its
-// configuration): the device keeps a float16 copy of the rows (+ 50 % of their memory) and a batch search reads a
+// configuration): the device keeps a float16 copy of the rows (+ 50 % of their memory) and a batch search (a filtered one only with SDB_TUNE_SKETCH_FILTERED) reads a
 // neighbour's float32 row only when its float16 distance does not prove that AddWithLimit discards it
 // (distset.go:184).  Same answers, bit for bit; 1.50 M against 1.07 M queries/s at 1M x 384.  On like in the library;
 // false switches it off explicitly (and frees the copy).

@@ -167,6 +167,7 @@ struct sdb_index {
   // them once under the shared lock); the conversion kernel runs outside it, serialised against the knob by sketch_mu.
   // Best-effort: no room for it (build_sketch's headroom rule) or a device error while building it leaves it off and
   // the walk reads float32 rows -- never a failed write.
+  bool tune_sketch_filtered = false;  // SDB_TUNE_SKETCH_FILTERED: filtered batch searches take the hop too (opt-in: its speed against the float32 walk is not measured)
   uint32_t tune_sketch = 1;  // 0 off (the copy is freed), 1 on (default), 2 on + audit (every discarded neighbour is evaluated exactly as well and checked)
   uint16_t *d_sketch = nullptr;
   float *d_sketch_norm = nullptr;  // [sketch_cap] ||y16||^2 per row (the euclidean form of the first stage)

@@ -552,23 +552,37 @@ static int launch_wide(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
   return launch_wide_w<NG, L2, 8>(a, nq, stream);
 }
 
+// The two-precision hop's kernel (SearchArgs::sketch): batch walks, plain and -- where the caller of launch_greedy_search
+// handed the copy to a filtered call (SDB_TUNE_SKETCH_FILTERED) -- filtered searches.  A filtered call keeps the hop up to
+// searchSize 128 (the two array registers of the kernel), also at 97 .. 128, where search_uses_hash() sends plain calls
+// to the bitset kernel: the LDS sets spill to the query's bitsets by themselves (HashVisited::spill clears the bitset
+// first), so such a call needs no bitset cleared ahead either (sketch_walk() is asked by the launcher and by the clear).
+bool sketch_walk(const SearchArgs &a, uint32_t nq) {
+  if (!a.sketch || a.pq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
+  if (!(a.ng == 1 || a.ng == 2 || a.ng == 3 || a.ng == 4 || a.ng == 6)) return false;
+  if (wide_walk(a, nq)) return false;
+  return search_uses_hash(a, nq) || (a.filt_off && !a.prefer_bitset);
+}
+
 template <int NG, bool L2>
 static int launch_plain(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
   if constexpr (NG >= 1 && NG <= 8)
     if (wide_walk(a, nq)) return launch_wide<NG, L2>(a, nq, stream);
-  if (search_uses_hash(a, nq)) {
-    // the two-precision hop (SearchArgs::sketch): batch walks, plain searches
-    if constexpr (NG == 1 || NG == 2 || NG == 3 || NG == 4 || NG == 6)
-      if (a.sketch && !a.filt_off && !a.vis_slots && !a.dcache && a.tail == 0 && a.search_size <= 128) {
-        // (few float32 rows survive the first stage: four pairs of them in flight per round leave the registers to the float16 rows)
-        using SkDist = PlainDist<NG, L2, true, 4, true>;
-        hipLaunchKernelGGL((k_greedy_search<SkDist, 2, false, kHashCap>), dim3(nq), dim3(64),
-                           HashVisited<kHashCap>::kWords * sizeof(uint32_t) + SkDist::kLdsBytes, stream, a);
-        SDB_HIP(hipGetLastError());
-        return SDB_OK;
-      }
-    return launch_nreg<PlainDist<NG, L2, true>, kHashCap>(a, nq, stream, PlainDist<NG, L2, true>::kLdsBytes);
-  }
+  const bool hash = search_uses_hash(a, nq);
+  if constexpr (NG == 1 || NG == 2 || NG == 3 || NG == 4 || NG == 6)
+    if (sketch_walk(a, nq)) {
+      // (few float32 rows survive the first stage: four pairs of them in flight per round leave the registers to the float16 rows)
+      using SkDist = PlainDist<NG, L2, true, 4, true>;
+      const size_t lds = HashVisited<kHashCap>::kWords * sizeof(uint32_t) + SkDist::kLdsBytes;
+      if (a.filt_off)  // all three filter forms; the threshold is search_kernel.h list_tail_bound
+        hipLaunchKernelGGL((k_greedy_search<SkDist, 2, true, kHashCap>), dim3(nq), dim3(64),
+                           lds + HashVisited<kHashCapResult>::kWords * sizeof(uint32_t), stream, a);
+      else
+        hipLaunchKernelGGL((k_greedy_search<SkDist, 2, false, kHashCap>), dim3(nq), dim3(64), lds, stream, a);
+      SDB_HIP(hipGetLastError());
+      return SDB_OK;
+    }
+  if (hash) return launch_nreg<PlainDist<NG, L2, true>, kHashCap>(a, nq, stream, PlainDist<NG, L2, true>::kLdsBytes);
   return launch_nreg<PlainDist<NG, L2, false>, 0>(a, nq, stream, PlainDist<NG, L2, false>::kLdsBytes);
 }
 
@@ -1925,7 +1939,8 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
   {
     const uint32_t knob = ix->tune_sketch;
     const uint16_t *sk = ix->d_sketch;
-    if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx && !filtered)
+    if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx &&
+        (!filtered || ix->tune_sketch_filtered))  // (filtered calls: opt-in, SDB_TUNE_SKETCH_FILTERED)
       a.sketch = sk, a.sketch_norm = ix->d_sketch_norm, a.sk_emax = ix->sk_emax, a.sk_ymax = ix->sk_ymax,
       a.sk_audit = knob == 2 ? 1u : 0u, a.sk_counters = ix->d_sk_counters;
   }
@@ -1940,7 +1955,7 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
       a.pq_lut_in_lds = ((size_t)pq->M * pq->K * sizeof(float) <= 64 * 1024) ? 1u : 0u;
     }
     // ClearAll (distset.go:101); the LDS hash variant clears a bitset only for a query that overflows it
-    if (!search_uses_hash(a, (uint32_t)nq))
+    if (!search_uses_hash(a, (uint32_t)nq) && !sketch_walk(a, (uint32_t)nq))
       SDB_HIP(hipMemsetAsync(ws->bitsets, 0, filtered ? 2 * bs_bytes : bs_bytes, stream));
     const bool prof = ix->profiling && !ix->ev0.empty();
     const uint32_t slot = (uint32_t)(ix->prof_count % sdb_index::kProfRing);
@@ -2120,6 +2135,9 @@ int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
       if (!ix->in_tx && !ix->sketch_current()) ix->build_sketch(nullptr, 0, true);  // inside a transaction: its commit builds it
       return SDB_OK;
     }
+    case SDB_TUNE_SKETCH_FILTERED:
+      ix->tune_sketch_filtered = value != 0;
+      return SDB_OK;
     case SDB_TUNE_NO_DEFER:
       ix->tune_no_defer = value != 0;
       return SDB_OK;

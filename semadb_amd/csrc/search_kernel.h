@@ -1413,9 +1413,36 @@ __device__ __forceinline__ float list_tail(const float (&cd)[NREG], int cap) {
   return t;
 }
 
+// The filtered walk's array is NOT sorted (its seeds are appended by Add, distset.go:203-211, and AddWithLimit bubbles a
+// point left only while it is `<` its neighbour, :193-198), so its last distance can RISE while a chunk's points are
+// inserted: the new last entry is the old second-to-last one.  What holds instead: one kept insertion puts x <= tail
+// somewhere and shifts the entries behind it right by one, so the last m + 1 entries of the new array lie within {x}
+// plus the last m + 2 of the old one, and x is at most one of those -- by induction the tail after j insertions is at
+// most the maximum of the ORIGINAL last j + 1 entries.  The i-th of a chunk's k new neighbours meets the array after at
+// most i <= k - 1 insertions: a neighbour whose distance is above the maximum of the last min(k, cap) distances, as the
+// chunk starts, is discarded at its turn whatever happens before it.  (Sorted array: that maximum is the tail.)
+// A NaN among those distances makes the result NaN (`d > NaN` is false: nothing is discarded in that chunk) -- a plain
+// fmaxf reduction would drop it.  Wave-uniform result.
+template <int NREG>
+__device__ __forceinline__ float list_tail_bound(const float (&cd)[NREG], int cap, int k, int lane) {
+  const int first = k < cap ? cap - k : 0;
+  float m = __int_as_float(0xff800000);  // -inf
+  bool nan = false;
+#pragma unroll
+  for (int r = 0; r < NREG; r++) {
+    const int e = r * 64 + lane;
+    if (e >= first && e < cap) nan |= cd[r] != cd[r], m = fmaxf(m, cd[r]);
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  return __ballot(nan) ? __int_as_float(0x7fc00000) : m;
+}
+
 // AddWithLimit (distset.go:184-198) over the lanes in `pd`, IN LANE ORDER, each lane holding (idreg,
-// mydist).  Only points that beat the current tail are replayed: the tail only shrinks, so a point that
-// fails the current threshold can never pass a later one.
+// mydist).  Every pending lane is tested against the tail AS IT IS NOW, again after every insertion, and the first that
+// passes is inserted; the lanes in front of it failed the tail they met at their turn and are dropped.  The re-test is
+// what makes this the reference's replay for an UNSORTED array too (the filtered walk's: there the tail can rise with
+// an insertion, and a lane behind the inserted one may pass a tail that an earlier tail would have refused).
 template <int NREG>
 __device__ __forceinline__ void add_with_limit_lanes(uint32_t (&cid)[NREG], float (&cd)[NREG], int &len, int cap,
                                                      uint32_t idreg, float mydist, uint64_t pd, int lane) {
@@ -2044,11 +2071,14 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
       if (pend) {
         n_dist += (uint32_t)__popcll(pend);
         if constexpr (sketch_policy<Dist>::value) {
-          // two-precision hop: with the array full, the neighbours whose float16 distance is provably above its last
-          // distance -- as it is NOW: it only falls while this row's points are inserted -- are discarded here;
-          // AddWithLimit would discard them one by one (distset.go:184) and nothing else ever reads their distance
+          // two-precision hop: with the array full, the neighbours whose float16 distance is provably above every last
+          // distance the array can have at their turn are discarded here; AddWithLimit would discard them one by one
+          // (distset.go:184) and nothing else ever reads their distance.  Plain walk: the array is sorted, its last
+          // distance only falls while this row's points are inserted, the threshold is the last distance as it is now.
+          // Filtered walk: the array is unsorted and its last distance can RISE within the chunk; the threshold is the
+          // maximum of its last min(k, cap) distances for the chunk's k new neighbours (list_tail_bound).
           if (len == cap) {
-            const float tail_d = list_tail(cd, cap);
+            const float tail_d = FILT ? list_tail_bound(cd, cap, __popcll(pend), lane) : list_tail(cd, cap);
             uint64_t out = 0;
             const uint64_t keep = dist.sketch_keep(a, nb, pend, lane, tail_d, out);
             if (cold_args(a).sk_audit) {  // (rare path: counted at once, not carried in a register through the walk)

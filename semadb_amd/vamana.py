@@ -167,7 +167,7 @@ class IndexVamana:
 
     TUNING = {"hub_min": 1, "hash_limit": 2, "no_hash": 3, "no_tile": 4, "no_mfma": 5, "wide_hash": 6, "hash16_probes": 7,
               "pq_narrow": 8, "wide_walk": 9, "host_filters": 10, "no_defer": 11, "no_zero_copy": 12,
-              "sketch": 13}  # SDB_TUNE_* (semadb_amd.h)
+              "sketch": 13, "sketch_filtered": 14}  # SDB_TUNE_* (semadb_amd.h)
 
     def sketch_stats(self):
         """(neighbours discarded on their float16 distance, contradicted by the exact distance [audit], copy in use)"""

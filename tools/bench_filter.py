@@ -2,7 +2,12 @@
 """Filtered search (search.go:33-51,93-95) at C2: 1M x 384 cosine, searchSize 75, batch 1024, filters of 10 / 1 000 /
 100 000 ids per query.  Reports the K2 kernel time (HIP events around the launch) and the whole call (which includes the
 host-side translation of the filter ids to slots -- filter arrays are host memory in the ABI, like the reference's
-roaring bitmap).  BENCH_TUNE=no_hash=1 gives the bitset variant of round 2 for comparison."""
+roaring bitmap).  BENCH_TUNE=no_hash=1 gives the bitset variant of round 2 for comparison.
+
+--sketch: the two-precision hop on filtered calls against the float32 walk (SDB_TUNE_SKETCH 1 against 0) in ONE process,
+the two alternating --reps times per filter size: per repetition the mean kernel and call time of three batches, their
+minimum and median per knob, the spread (max - min) of the knob-0 repetitions -- the yardstick a difference has to beat --
+and the neighbours discarded on their float16 distance over the distances the reference evaluates."""
 import argparse
 import json
 import os
@@ -22,6 +27,8 @@ ap.add_argument("--sizes", default="10,1000,100000")
 ap.add_argument("--holes", type=int, default=0, help="delete this many rows first: ids are no longer consecutive (id -> slot table on the device)")
 ap.add_argument("--host-filters", action="store_true", help="the host's translation (tuning host_filters)")
 ap.add_argument("--pinned", action="store_true", help="the filter arrays in page-locked host memory (what sdb_host_alloc gives a host program)")
+ap.add_argument("--sketch", action="store_true", help="knob 0 against knob 1, alternating in this process (see above)")
+ap.add_argument("--reps", type=int, default=5, help="--sketch: repetitions per knob and filter size")
 a0 = ap.parse_args()
 
 
@@ -60,6 +67,43 @@ for size in [int(x) for x in a0.sizes.split(",")]:
         keep = torch.from_numpy(flat.view(np.int64)).pin_memory()  # `keep` owns the pages
         flat = keep.numpy().view(np.uint64)
         out["pinned"] = True
+    if a0.sketch:
+        try:
+            ix.set_tuning("sketch_filtered", 1)  # (the filtered hop is an opt-in)
+        except Exception:  # a library from before the knob (a comparison run): both knobs time its float32 filtered walk
+            out["sketch_filtered_knob"] = False
+        rec = {0: {"kernel_ms": [], "call_ms": []}, 1: {"kernel_ms": [], "call_ms": []}}
+        for rep in range(a0.reps):
+            for knob in (0, 1):
+                ix.set_tuning("sketch", knob)  # (0 drops the float16 copy, 1 converts the rows again: outside the timed region)
+                for _ in range(3 if rep == 0 else 1):
+                    ix.search_batch(queries[0], 10, 75, filters=(off, flat))
+                    torch.cuda.synchronize()
+                ix.profile_read()
+                dt = 0.0
+                for b in range(1, 4):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    ix.search_batch(queries[b], 10, 75, filters=(off, flat))
+                    torch.cuda.synchronize()
+                    dt += time.perf_counter() - t0
+                rec[knob]["kernel_ms"].append(round(float(np.mean(ix.profile_read())), 4))
+                rec[knob]["call_ms"].append(round(dt / 3 * 1e3, 3))
+        before = ix.sketch_stats()[0]  # (the knob is at 1)
+        _, _, _, tr = ix.search_batch(queries[1], 10, 75, filters=(off, flat), trace=True)
+        torch.cuda.synchronize()
+        discarded, _, in_use = ix.sketch_stats()
+        n_dist = int(tr.n_dist.sum().item())
+        row = {"copy_in_use": bool(in_use), "discarded": int(discarded - before), "n_dist": n_dist,
+               "discarded_over_n_dist": round((discarded - before) / max(n_dist, 1), 4)}
+        for knob in (0, 1):
+            k = rec[knob]["kernel_ms"]
+            row["sketch_%d" % knob] = {"kernel_ms": k, "kernel_ms_min": min(k), "kernel_ms_median": round(float(np.median(k)), 4),
+                                       "call_ms": rec[knob]["call_ms"], "call_ms_median": round(float(np.median(rec[knob]["call_ms"])), 3)}
+        row["sketch_0_kernel_spread_ms"] = round(max(rec[0]["kernel_ms"]) - min(rec[0]["kernel_ms"]), 4)
+        row["kernel_median_1_over_0"] = round(row["sketch_1"]["kernel_ms_median"] / row["sketch_0"]["kernel_ms_median"], 4)
+        out["filter_%d" % size] = row
+        continue
     for _ in range(3):  # the first filtered calls size their workspaces (bitsets for the spill path, filter arrays)
         ix.search_batch(queries[0], 10, 75, filters=(off, flat))
         torch.cuda.synchronize()
