@@ -158,13 +158,18 @@ def run_model(orc, g, metric, queries, limit, L, filters, emax_ymax=None):
     return reps, t
 
 
-def check_tally(t, what, sandwich=True):
+def check_tally(t, what, sandwich=True, naive=True):
     """the model's own conditions.  sandwich: the two sides within 1 % of each other, something provably discarded, and
-    the input catches the naive rule (a neighbour the chunk-start tail would discard and the reference keeps)"""
+    -- unless naive is False -- the input catches the naive rule (a neighbour the chunk-start tail would discard and the
+    reference keeps).  naive = False is for searchSize 1 alone: an array of one entry is sorted, B is its only distance,
+    so the two rules are the same rule there and no input can tell them apart."""
     assert t.lower <= t.upper <= t.discardable <= t.full, "%s: %r" % (what, t)
     if sandwich:
         assert t.lower > 0 and t.lower >= 0.99 * t.upper, "%s: %r" % (what, t)
-        assert t.naive_wrong > 0, "%s: the chunk-start tail discards nothing wrongly here: %r" % (what, t)
+        if naive:
+            assert t.naive_wrong > 0, "%s: the chunk-start tail discards nothing wrongly here: %r" % (what, t)
+        else:
+            assert t.naive_wrong == 0 and t.risen == 0, "%s: %r" % (what, t)
 
 
 # ---------------------------------------------------------------------------------------------- the inputs
@@ -176,13 +181,33 @@ class Case:
         self.queries, self.filters, self.limit, self.L, self.sandwich = queries, filters, limit, L, sandwich
         self.g = Graph(*ex)
         self.emax_ymax = None if maxima_rows is None else maxima(maxima_rows)
+        self.naive = L != 1  # (check_tally: an array of one entry is sorted)
         self._model = None
+        self._prefixes = {}
 
     def model(self, orc):
         """([Replay], Tally), computed once"""
         if self._model is None:
             self._model = run_model(orc, self.g, self.metric, self.queries, self.limit, self.L, self.filters, self.emax_ymax)
         return self._model
+
+    def check(self, t):
+        check_tally(t, self.what, self.sandwich, self.naive)
+
+    def prefix(self, orc, nq):
+        """([Replay], Tally) of the batch's first `nq` queries, from the same replays as the whole batch's"""
+        if nq not in self._prefixes:
+            D = orc.distance_matrix(self.queries[:nq], self.g.vecs, self.metric, impl_of(orc))
+            v16 = half_rows(self.g.vecs)
+            with np.errstate(all="ignore"):
+                yy16 = (v16 ** 2).sum(1)
+            emax, ymax = maxima(self.g.vecs) if self.emax_ymax is None else self.emax_ymax
+            reps = self.model(orc)[0][:nq]
+            t = Tally()
+            for i in range(nq):
+                count(t, Bounds(self.metric, self.queries[i], v16, yy16, emax, ymax), D[i], reps[i])
+            self._prefixes[nq] = (reps, t)
+        return self._prefixes[nq]
 
 
 def latent_rows(rng, n, d):
@@ -228,7 +253,9 @@ def _graph(orc, metric, d, full_rows):
     return o.export(), o
 
 
-WIDTH_CASES = [(m, d, False) for d in (128, 384, 768) for m in METRICS] + [(m, 384, True) for m in METRICS]
+# NG 1 (32: short, 128), 2 (160: padded, 256), 3, 4, 6 (640: padded, 768); full rows at NG 3 and 4
+WIDTH_CASES = [(m, d, False) for d in (128, 384, 768, 32, 160, 256, 512, 640) for m in METRICS] + \
+              [(m, d, True) for d in (384, 512) for m in METRICS]
 
 
 @functools.lru_cache(maxsize=None)
@@ -242,8 +269,11 @@ def width_case(orc, metric, d, full_rows, limit=10, L=40):
     return Case(what, metric, d, ex, o, queries, filters, limit, L)
 
 
-L_CASES = ((10, 10), (128, 10))  # (L, limit); L = 40 is the width cases'
+# (L, limit); L = 40 is the width cases'.  1 and 2: min(k, L) is the whole array; 96 / 97: the last searchSize with the
+# LDS hash set by routing and the first without (index.hip search_uses_hash) -- a filtered call keeps the hop on both sides
+L_CASES = ((1, 1), (2, 1), (5, 5), (10, 10), (64, 10), (96, 10), (97, 10), (128, 10))
 L_NO_STAGE = 129                 # past the kernel's two array registers: the float32 walk
+L_REFUSED = (5, 10)              # searchSize < limit: refused by both sides (search.go:23-25)
 
 
 @functools.lru_cache(maxsize=None)
@@ -311,3 +341,143 @@ def dispatch_case(orc):
     queries = unit_rows(rng, 513, 128)
     filters = make_filters(rng, ex[0][ex[0] != 1].astype(np.int64), 513, 40)
     return Case("default dispatch", "cosine", 128, ex, o, queries, filters, 10, 40)
+
+
+DISPATCH_SIZES = (8, 64, 513)
+
+
+@functools.lru_cache(maxsize=None)
+def dispatch_beyond_hash_case(orc):
+    """513 queries at searchSize 100 on the d = 128 cosine table; calls of 8 and 64 queries share the first ones"""
+    ex, o = _graph(orc, "cosine", 128, False)
+    rng = np.random.default_rng(9228)
+    queries = unit_rows(rng, 513, 128)
+    filters = make_filters(rng, ex[0][ex[0] != 1].astype(np.int64), 513, 100)
+    return Case("default dispatch, L = 100", "cosine", 128, ex, o, queries, filters, 10, 100)
+
+
+@functools.lru_cache(maxsize=None)
+def _overflow(orc, metric):
+    ex, queries = M.overflow_case(orc, metric)
+    return ex, queries, M.load_oracle(orc, metric, 128, ex)
+
+
+OVERFLOW_L = ((1, 1), (2, 1), (20, 10), (40, 10))  # (L, limit)
+
+
+@functools.lru_cache(maxsize=None)
+def overflow_case(orc, metric, L, limit):
+    """a start node with an overflow list (more than 64 + 64 edges; tests/two_precision_model.py overflow_case): one
+    expansion is several chunks, between which the array's last distance moves -- and, unsorted, can rise"""
+    ex, queries, o = _overflow(orc, metric)
+    rng = np.random.default_rng(_seed(metric, 128, 5) + L)
+    filters = make_filters(rng, ex[0][ex[0] != 1].astype(np.int64), N_QUERIES, L)
+    return Case("%s overflow list L=%d limit=%d" % (metric, L, limit), metric, 128, ex, o, queries, filters, limit, L)
+
+
+HOSTILE_KINDS = M.HOSTILE_NO_DISCARD + M.HOSTILE_SANDWICH
+HOSTILE_TABLES = [(m, d) for d in (128, 512) for m in ("cosine", "euclidean")]
+
+
+@functools.lru_cache(maxsize=None)
+def hostile_case(orc, metric, d, kind):
+    """8 queries that break or strain the float16 copy of the query (tests/two_precision_model.py hostile_queries) with
+    the first 8 filters of the width case.  Only the order of the counts is asserted of the model (sandwich = False): a
+    bound that is infinite, NaN or wider than the distances proves nothing, and upper == 0 then makes the device's 0."""
+    base = width_case(orc, metric, d, False)
+    q = M.hostile_queries(d, kind)
+    return Case("%s d=%d hostile %s" % (metric, d, kind), metric, d, base.ex, base.o, q, base.filters[:q.shape[0]], 10, 40,
+                sandwich=False)
+
+
+# ---------------------------------------------------------------------------------------------- the write paths
+class Step:
+    """one write of the write-path schedule: `ops` for the device -- ("iud", [(id, row or None)]) applied through
+    InsertUpdateDelete one point per round, ("tx", ids, rows) inserted inside begin_write .. commit, ("delete", ids),
+    ("compact",) -- and the checkpoint behind it: a Case over the oracle's graph after the same write, the maxima the
+    device carries, whether anything can be discarded"""
+
+    def __init__(self, what, ops, case, expect_none):
+        self.what, self.ops, self.case, self.expect_none = what, ops, case, expect_none
+
+
+def _scaled(rng, n, d, norm):
+    return (unit_rows(rng, n, d) * np.float32(norm)).astype(np.float32)
+
+
+WRITE_GROWS_PAST = 2048  # the 1 501 rows loaded sit in a table of 2 048 (capacities double from 1 024): the transaction grows it
+
+
+@functools.lru_cache(maxsize=None)
+def write_path_steps(orc, metric):
+    """The filtered twin of test_gpu_two_precision_bound.py::test_maxima_through_every_write_path, shorter.  The maxima
+    are those of every row converted since the last full conversion (load, compact), deleted rows included.  Each
+    checkpoint's filters are drawn over the live ids, and every one of them also names ids the last write deleted,
+    updated and added."""
+    d, L, limit = 128, 40, 10
+    ex0, o_loaded = _graph(orc, metric, d, False)
+    o = M.load_oracle(orc, metric, d, ex0, L=40)  # (this one is written to; R = 64 from here on, on both sides)
+    rng = np.random.default_rng(_seed(metric, d, 6))
+    queries = unit_rows(rng, N_QUERIES, d)
+    state = {"maxima": maxima(ex0[1]), "next": 5000}
+    steps = []
+
+    def checkpoint(what, ops, deleted=(), updated=(), added=(), expect_none=False, full_conversion=False):
+        ex = o.export()
+        if full_conversion:
+            state["maxima"] = maxima(ex[1])
+        live = ex[0][ex[0] != 1].astype(np.int64)
+        named = set(int(v) for v in list(deleted)[:3] + list(updated)[:3] + list(added)[:3])
+        filters = [f | named for f in make_filters(rng, live, N_QUERIES, L)]
+        c = Case("%s write path: %s" % (metric, what), metric, d, ex, M.load_oracle(orc, metric, d, ex), queries, filters,
+                 limit, L, sandwich=not expect_none)
+        c.emax_ymax = state["maxima"]
+        steps.append(Step(what, ops, c, expect_none))
+
+    def apply(changes):
+        """InsertUpdateDelete's order (fuzz_parity.trial): inserts, then deletes and updates' old rows, then the updates"""
+        have = set(int(v) for v in o.export(with_vectors=False)[0])
+        for i, row in changes:
+            if row is not None and i not in have:
+                assert o.insert(i, row) == 0
+        gone = [i for i, row in changes if i in have]
+        if gone:
+            assert o.delete(np.array(gone, dtype=np.uint64)) == 0
+        for i, row in changes:
+            if row is not None and i in have:
+                assert o.insert(i, row) == 0
+        rows = [row for _, row in changes if row is not None]
+        if rows:
+            state["maxima"] = M.join_maxima(state["maxima"], maxima(np.stack(rows)))
+
+    def new_ids(k):
+        first = state["next"]
+        state["next"] += k
+        return list(range(first, first + k))
+
+    checkpoint("load", [])
+    ins, upd, dele = new_ids(3), [100, 101], [200, 201, 202]
+    changes = [(i, r) for i, r in zip(ins, _scaled(rng, 3, d, 8.0))] + [(i, None) for i in dele] + \
+              [(i, r) for i, r in zip(upd, _scaled(rng, 2, d, 1e-3))]
+    apply(changes)
+    checkpoint("InsertUpdateDelete, inserts of norm 8, updates of norm 1e-3, deletes", [("iud", changes)], dele, upd, ins)
+    ids, rows = new_ids(560), _scaled(rng, 560, d, 1e-3)
+    apply(list(zip(ids, rows)))
+    checkpoint("begin_write .. commit that grows the table, norm 1e-3", [("tx", ids, rows)], added=ids)
+    big = new_ids(1)
+    row = unit_rows(rng, 1, d)
+    row[0, 17] = 1e6
+    apply([(big[0], row[0])])
+    checkpoint("a row with an element of 1e6", [("iud", [(big[0], row[0])])], added=big, expect_none=True)
+    apply([(big[0], None)])
+    checkpoint("that row deleted", [("delete", big)], deleted=big, expect_none=True)
+    checkpoint("compact", [("compact",)], deleted=big, full_conversion=True)
+    return steps
+
+
+@functools.lru_cache(maxsize=None)
+def reader_case(orc):
+    """the table, queries and filters of the reader-during-commits test, and the rows the writer adds one by one"""
+    base = width_case(orc, "cosine", 128, False)
+    rng = np.random.default_rng(9333)
+    return base, _scaled(rng, 10, 128, 1.0)

@@ -1,7 +1,9 @@
 """Randomised differential trials (tools/fuzz_parity.py: device through the C ABI vs the oracle over random shapes,
 metrics, parameters, data with ties and duplicates, build schedules, write sequences in rounds or one by one, a
 quantizer attached mid-way; graphs edge for edge, plain / filtered / exact-scan searches and K1 bit for bit; plus
-random product-quantizer fits / codecs and shard merges).
+random product-quantizer fits / codecs and shard merges; plus one table per trial through the two-precision walks, plain
+and filtered, held to the float64 models -- two_precision_trial; tests/test_two_precision_fuzz_model.py runs the same
+draws without a GPU and asserts that the models prove something on them).
 
 The soak's first runs exposed two defects, each now pinned by a deterministic test of its own:
   * a delete leaving more stragglers than the start node's 64-entry row holds (the reference's start node has no
@@ -37,3 +39,5 @@ def test_fuzz_short_soak(oracle, monkeypatch, seed):
         fz.pq_trial(rng)
         fz.flat_trial(rng)
         fz.trial(rng, t)
+        # (a stream of its own: the four trials above draw what they drew before this one existed)
+        fz.two_precision_trial(np.random.default_rng([seed, t, 2]))

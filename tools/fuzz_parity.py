@@ -4,6 +4,10 @@ same index on both sides (sequentially or in the batched round schedule), applie
 switches the store to a product quantizer, and after every stage compares the exported graphs edge for edge and
 a batch of searches (plain and filtered) id for id, distance bit for distance bit, visit for visit.
 
+Every trial also draws a table for the two-precision hop (two_precision_trial): the one-wave walk with its float16
+first stage, plain and filtered, against the float64 models of tests/two_precision_model.py and
+tests/filtered_two_precision_model.py -- answers, and the number of neighbours discarded between the models' two counts.
+
   python tools/fuzz_parity.py --trials 200 --seed 1      (prints one JSON line; exit code 1 on the first mismatch)
 """
 import argparse
@@ -299,6 +303,271 @@ def trial(rng, t):
     return desc
 
 
+# ---------------------------------------------------------------------------------------------- the two-precision hop
+TP_QUERIES = 32
+TP_HOSTILE = ("overflow", "nan", "inf", "zero", "tiny", "norm1e4", "norm1e-4")
+
+
+def _tp_same_bits(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(bits(a)[~na], bits(b)[~nb])
+
+
+def _tp_equals_replay(ans, reps, tag):
+    """per query: ids, distance bits (NaN where the reference has NaN), counts, n_dist / n_hop / n_edges, visit order"""
+    ids, dd, c, tr = ans
+    for i, r in enumerate(reps):
+        k = len(r.ids)
+        assert int(c[i]) == k, (tag, "count", i)
+        assert np.array_equal(ids[i, :k], r.ids), (tag, "ids", i)
+        assert _tp_same_bits(dd[i, :k], r.dists), (tag, "dist bits", i)
+        assert (int(tr.n_dist[i]), int(tr.n_hop[i]), int(tr.n_edges[i])) == (r.n_dist, r.n_hop, r.n_edges), (tag, "counters", i)
+        assert np.array_equal(tr.visit_ids[i, :r.n_hop], r.visit), (tag, "visit order", i)
+
+
+def _tp_walk(g, q, limit, sl, filters):
+    d0, c0, _ = g.sketch_stats()
+    ans = g.search_batch(q, limit, sl, filters=filters, trace=True, visit_cap=4096)
+    d1, c1, in_use = g.sketch_stats()
+    return ans, d1 - d0, c1 - c0, in_use
+
+
+def two_precision_trial(rng, device=True):
+    """One random table through the kernels that have the float16 first stage (k_greedy_search<PlainDist<NG, .., true>>,
+    plain and filtered), held to the float64 models: the replays equal the oracle's walks; on the device the answers
+    equal the replays, no discard is contradicted by the audit, and the number discarded lies between the models' two
+    counts, taken with the maxima the device carries (every row converted since the last full conversion, deleted ones
+    included).  The routing is stated here, not imported: the stage runs when the width has it, no quantizer is attached
+    (none is, here), no transaction is open, and searchSize <= 96 for a plain call / <= 128 for a filtered one -- on the
+    one-wave kernel, which wide_walk = 1 selects at every batch size and the default dispatch only where the many-waves
+    kernel is out (a filtered call with searchSize > 96).  device=False: everything except the device.
+    Returns {"desc": .., "batches": [{"stage", "plain": (lower, discarded, upper), "filtered": (..)}]}."""
+    from tests import filtered_two_precision_model as F
+    from tests import two_precision_model as M
+    no_stage = int(rng.integers(0, 6)) == 0
+    d = int(rng.choice(M.NO_STAGE_WIDTHS if no_stage else M.WIDTHS))
+    metric = str(rng.choice(METRICS))
+    kind = str(rng.choice(["unit", "latent", "grid", "dups"], p=[0.35, 0.35, 0.15, 0.15]))
+    R = int(rng.integers(4, 65))
+    L = int(rng.integers(max(R // 2, 5), 101))
+    alpha = float(rng.choice([1.0, 1.1, 1.2, 1.5]))
+    n = int(rng.integers(200, min(2000, 300000 // d) + 1))
+    batched = bool(rng.integers(0, 2))
+    big_min = int(rng.choice([2, 3, 8, 512]))
+    round_size = int(rng.choice([0, 0, 17, 64, 300]))
+    by_load = bool(rng.integers(0, 2))
+    # one trial in three where the rows allow it: a table created one doubling short (capacities are 1 024 x 2^k) and
+    # filled to just below it, so that the first write grows it
+    tight = int(rng.integers(0, 3)) == 0 and 300000 // d >= 1023
+    if tight:
+        n = 1023 - int(rng.integers(0, 9))
+    bitmap_batch = int(rng.integers(0, 2))
+    desc = dict(two_precision_trial=True, d=d, metric=metric, kind=kind, R=R, L=L, alpha=alpha, n=n, batched=batched,
+                big_min=big_min, round_size=round_size, by_load=by_load, tight=tight)
+    CURRENT.clear()
+    CURRENT.update(desc)
+    if VERBOSE:
+        print("  two-precision:", desc, file=sys.stderr, flush=True)
+
+    def rows(k):
+        """k rows of the trial's kind; one batch in three scaled, so that the table-wide maxima move"""
+        x = draw_rows(rng, max(k, 1), d, kind)
+        if int(rng.integers(0, 3)) == 0:
+            x = (x * np.float32(rng.choice([1e-3, 2.0, 32.0]))).astype(np.float32)
+        return x
+
+    impl = M.impl_of(orc)
+    sv = start_vector(np.random.default_rng(int(rng.integers(1 << 30))), d)
+    o = orc.Index(d, metric, R, L, alpha, impl=impl)
+    o.set_start(sv)
+    base = rows(n)
+    ids = np.arange(2, n + 2, dtype=np.uint64)
+    if batched:
+        assert o.insert_rounds(ids, base, round_size=round_size, big_min=big_min) == 0
+    else:
+        for i in range(n):
+            assert o.insert(int(ids[i]), base[i]) == 0
+    g = None
+    if device:
+        g = vamana.NewIndexVamana("tp", vamana.IndexVectorVamanaParameters(d, metric, L, R, alpha),
+                                  capacity=1024 if tight else 0, strict=False)
+        g.set_tuning("hub_min", big_min)
+        g.set_tuning("sketch_filtered", 1)
+    out = {"desc": desc, "batches": [], "start_degree": 0}
+    state = {"maxima": None, "last": None, "in_tx_done": False}
+
+    def batch(tag, live, gone, with_bitmaps):
+        """32 queries after a committed write: models against the oracle, the device against the models"""
+        ex = o.export()
+        gr = M.Graph(*ex)
+        out["start_degree"] = max(out["start_degree"], int(gr.deg[gr.start]))
+        q = draw_rows(rng, TP_QUERIES, d, kind)
+        for pos, k in zip((7, 19), rng.choice(len(TP_HOSTILE), size=2, replace=False)):
+            q[pos] = M.hostile_queries(d, TP_HOSTILE[int(k)], seed=int(rng.integers(1 << 20)))[0]
+        limit = int(rng.integers(1, 21))
+        sl = int(rng.integers(limit, 129))
+        live_a = np.array(live, dtype=np.int64)
+        top = int(max(live + gone)) + 5000
+        filters = []
+        for f in F.make_filters(rng, live_a, TP_QUERIES, sl):
+            f = set(f) | set(top + int(v) for v in rng.integers(0, 1000, 3))  # unknown ids
+            if gone:
+                f |= set(int(v) for v in rng.choice(gone, size=min(3, len(gone)), replace=False))  # deleted ids
+            filters.append(f)
+        CURRENT["stage"] = "%s: limit %d searchSize %d" % (tag, limit, sl)
+        reps_p, t_p, _ = M.run_model(orc, gr, metric, q, limit, sl, state["maxima"])
+        reps_f, t_f = F.run_model(orc, gr, metric, q, limit, sl, filters, state["maxima"])
+        for i in range(TP_QUERIES):  # the replays are held to the oracle's own walks first
+            for r, fl in ((reps_p[i], None), (reps_f[i], sorted(filters[i]))):
+                o_ids, o_d, o_vis, o_tr = o.search(q[i], limit, sl, filter_ids=fl)
+                what = (tag, "replay != oracle", "plain" if fl is None else "filtered", i)
+                assert np.array_equal(r.ids, o_ids) and _tp_same_bits(r.dists, o_d) and np.array_equal(r.visit, o_vis), what
+                assert (r.n_hop, r.n_dist, r.n_edges) == (o_tr.n_hop, o_tr.n_dist, o_tr.n_edges), what
+        assert t_p.lower <= t_p.upper <= t_p.discardable <= t_p.full, (tag, "plain model", repr(t_p))
+        assert t_f.lower <= t_f.upper <= t_f.discardable <= t_f.full, (tag, "filtered model", repr(t_f))
+        stage = {"plain": not no_stage and sl <= 96, "filtered": not no_stage and sl <= 128}
+        rec = {"stage": stage, "plain": [t_p.lower, None, t_p.upper], "filtered": [t_f.lower, None, t_f.upper]}
+        state["last"] = (q, limit, sl, filters, reps_p, reps_f)
+        out["batches"].append(rec)
+        if not device:
+            return
+        forms = [("filtered", filters, reps_f, t_f)]
+        if with_bitmaps:
+            forms.append(("filtered", vamana.FilterBitmaps.from_sets(filters, align=int(rng.choice([1, 64]))), reps_f, t_f))
+        g.set_tuning("wide_walk", 1)
+        for walk, fl, reps, t in [("plain", None, reps_p, t_p)] + forms:
+            seen = []
+            for mode in (2, 1):
+                g.set_tuning("sketch", mode)
+                ans, discarded, contradicted, in_use = _tp_walk(g, q, limit, sl, fl)
+                what = (tag, walk, "bitmaps" if isinstance(fl, vamana.FilterBitmaps) else "", "sketch=%d" % mode,
+                        "lower %d / discarded on the device %d / upper %d, contradicted %d" % (t.lower, discarded, t.upper, contradicted))
+                assert in_use == (not no_stage), what
+                _tp_equals_replay(ans, reps, what)
+                assert contradicted == 0, what
+                if stage[walk]:
+                    assert t.lower <= discarded <= t.upper, what
+                else:
+                    assert discarded == 0, what
+                seen.append(discarded)
+            assert seen[0] == seen[1], (tag, walk, "the audit run discarded %d, the plain run %d" % tuple(seen))
+            rec[walk][1] = seen[1]
+        # the default dispatch: 32 queries are the many-waves kernel's (no stage) wherever it can take them, which is
+        # searchSize <= 96; beyond, a plain call is the bitset kernel's and a filtered one keeps the hop
+        g.set_tuning("wide_walk", 0)
+        ans, discarded, contradicted, _ = _tp_walk(g, q, limit, sl, None)
+        _tp_equals_replay(ans, reps_p, (tag, "default dispatch, plain"))
+        assert discarded == 0 and contradicted == 0, (tag, "default dispatch, plain: %d discarded" % discarded)
+        ans, discarded, contradicted, _ = _tp_walk(g, q, limit, sl, filters)
+        _tp_equals_replay(ans, reps_f, (tag, "default dispatch, filtered"))
+        what = (tag, "default dispatch, filtered", "lower %d / discarded on the device %d / upper %d" % (t_f.lower, discarded, t_f.upper))
+        assert contradicted == 0, what
+        if stage["filtered"] and sl > 96:
+            assert t_f.lower <= discarded <= t_f.upper, what
+        else:
+            assert discarded == 0, what
+        g.set_tuning("wide_walk", 1)
+
+    def inside_transaction():
+        """once per trial: no copy in use, nothing discarded, the committed version's answers"""
+        if not device or state["in_tx_done"]:
+            return
+        state["in_tx_done"] = True
+        q, limit, sl, filters, reps_p, reps_f = state["last"]
+        for fl, reps in ((None, reps_p), (filters, reps_f)):
+            ans, discarded, contradicted, in_use = _tp_walk(g, q, limit, sl, fl)
+            what = ("inside the open transaction", "plain" if fl is None else "filtered")
+            assert not in_use and discarded == 0 and contradicted == 0, what
+            _tp_equals_replay(ans, reps, what)
+
+    try:
+        if device:
+            if by_load:
+                g.load(*o.export())
+            else:
+                g.set_start(sv)
+                g.insert_batch(ids, base, round_size=round_size if batched else 1)
+            check_graph(g, o)
+        state["maxima"] = M.maxima(o.export()[1])  # a full conversion, or every row appended since the table was empty
+        live, gone = [int(v) for v in ids], []
+        batch("after build", live, gone, bitmap_batch == 0)
+        n_steps = int(rng.integers(1, 4))
+        for step in range(n_steps):
+            n_del = int(rng.integers(0, max(1, len(live) // 4)))
+            dels = [int(v) for v in rng.choice(live, size=n_del, replace=False)] if n_del else []
+            rest = sorted(set(live) - set(dels))
+            n_upd = int(rng.integers(0, min(10, len(rest)) + 1))
+            upds = [int(v) for v in rng.choice(rest, size=n_upd, replace=False)] if n_upd else []
+            upd_vecs = rows(n_upd)
+            n_ins = int(rng.integers(1, 40)) if rng.integers(0, 3) else int(rng.integers(40, 200))
+            if tight and step == 0:
+                n_ins = max(n_ins, 40)  # past 1 024 rows (deleted rows keep theirs until compact)
+            wr = int(rng.choice([1, 1, 0, 7, 64]))
+            new_vecs = rows(n_ins)
+            first_new = max(live + gone + [1]) + 1 + int(rng.integers(0, 3))
+            new_ids = list(range(first_new, first_new + n_ins))
+            explicit = bool(rng.integers(0, 2))
+            compact = int(rng.integers(0, 3)) == 0
+            CURRENT["stage"] = "step %d: %d inserts (round_size %d), %d deletes, %d updates, %s%s" % (
+                step, n_ins, wr, len(dels), len(upds), "begin_write .. commit" if explicit else "InsertUpdateDelete",
+                ", compact" if compact else "")
+            if device:
+                size_before = g.SizeInMemory()
+                if explicit:
+                    g.begin_write()
+                    g.insert_batch(np.array(new_ids, dtype=np.uint64), new_vecs[:n_ins], round_size=wr)
+                    if dels or upds:
+                        g.delete_batch(np.array(dels + upds, dtype=np.uint64))
+                    for k, i in enumerate(upds):
+                        g.insert_batch(np.array([i], dtype=np.uint64), upd_vecs[k:k + 1], round_size=1)
+                    inside_transaction()
+                    g.commit()
+                else:
+                    ch = [vamana.IndexVectorChange(i, new_vecs[k]) for k, i in enumerate(new_ids)]
+                    ch += [vamana.IndexVectorChange(i, None) for i in dels]
+                    ch += [vamana.IndexVectorChange(i, upd_vecs[k]) for k, i in enumerate(upds)]
+                    g.InsertUpdateDelete(ch, round_size=wr, _between=lambda tag: inside_transaction())
+                if tight and step == 0:
+                    assert g.SizeInMemory() > 1.5 * size_before, "the table did not grow"
+            if wr == 1:
+                for k, i in enumerate(new_ids):
+                    assert o.insert(i, new_vecs[k]) == 0
+            else:
+                assert o.insert_rounds(np.array(new_ids, dtype=np.uint64), new_vecs[:n_ins], round_size=wr, big_min=big_min) == 0
+            if dels or upds:
+                assert o.delete(np.array(dels + upds, dtype=np.uint64)) == 0
+            for k, i in enumerate(upds):
+                assert o.insert(i, upd_vecs[k]) == 0
+            # appended since the last full conversion: the new rows and the updates' new rows (the old ones stay counted)
+            state["maxima"] = M.join_maxima(state["maxima"], M.maxima(np.vstack([new_vecs[:n_ins], upd_vecs[:n_upd]])))
+            live = sorted((set(live) - set(dels)) | set(new_ids))
+            gone = gone + dels
+            if compact:
+                if device:
+                    g.compact()
+                    assert g.row_usage()[1] == 0
+                state["maxima"] = M.maxima(o.export()[1])  # every remaining row converted again
+            if device:
+                check_graph(g, o)
+            batch("after write step %d" % step, live, gone, bitmap_batch == 1 and step == 0)
+    finally:
+        if g is not None:
+            g.close()
+    return out
+
+
+def two_precision_sums(results):
+    """{walk: {"batches with the stage", "of them with lower > 0", "lower", "discarded", "upper"}} over trials' tallies"""
+    sums = {}
+    for walk in ("plain", "filtered"):
+        recs = [b[walk] for r in results for b in r["batches"] if b["stage"][walk]]
+        sums[walk] = {"batches_with_stage": len(recs), "with_lower_above_0": sum(1 for x in recs if x[0] > 0),
+                      "lower": sum(x[0] for x in recs), "discarded": sum(x[1] or 0 for x in recs), "upper": sum(x[2] for x in recs)}
+    sums["max_start_degree"] = max([r["start_degree"] for r in results] or [0])
+    return sums
+
+
 def merge_trial(rng):
     """the shard fan-out's merge (cluster/actions.go:357-376) on random ragged per-shard results with ties"""
     from semadb_amd import cluster
@@ -487,6 +756,7 @@ def main():
     t0 = time.time()
     done = 0
     dims = set()
+    two_precision = []
     for t in ([a.only] if a.only >= 0 else range(a.trials)):
         rng = np.random.default_rng([a.seed, t])
         try:
@@ -506,6 +776,9 @@ def main():
             if a.verbose:
                 print("trial %d: index %s" % (t, CURRENT), file=sys.stderr, flush=True)
             desc = trial(rng, t)
+            if a.verbose:
+                print("trial %d: two-precision" % t, file=sys.stderr, flush=True)
+            two_precision.append(two_precision_trial(np.random.default_rng([a.seed, t, 2])))  # (a stream of its own)
             if time.time() - t1 > 20:
                 print("slow trial %d: merge %.1fs, pq %.1fs %s, index %.1fs %s" % (
                     t, t2 - t1, t3 - t2, pq_desc, time.time() - t3, CURRENT), file=sys.stderr)
@@ -518,7 +791,7 @@ def main():
         if a.seconds and time.time() - t0 > a.seconds:
             break
     print(json.dumps({"trials_passed": done, "seed": a.seed, "seconds": round(time.time() - t0, 1),
-                      "distinct_dims": len(dims), "mismatches": 0}))
+                      "distinct_dims": len(dims), "mismatches": 0, "two_precision": two_precision_sums(two_precision)}))
 
 
 if __name__ == "__main__":
