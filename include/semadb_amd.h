@@ -23,7 +23,7 @@
  *     serves searches from concurrent goroutines under an RLock, shard/cache/manager.go:163), also
  *     while ONE thread writes (insert / delete): they see the last committed graph (see
  *     sdb_index_begin_write).  Writers are exclusive among themselves, like the shard's write lock;
- *     load / attach_pq / set_codes / set_start are maintenance calls with no search in flight.
+ *     load / attach_pq / attach_bq / set_codes / set_bit_codes / set_start are maintenance calls with no search in flight.
  */
 #ifndef SEMADB_AMD_H
 #define SEMADB_AMD_H
@@ -50,6 +50,10 @@ typedef enum {
 #define SDB_METRIC_EUCLIDEAN 0
 #define SDB_METRIC_COSINE 1
 #define SDB_METRIC_DOT 2
+/* models.Distance* names accepted by distance.GetBitDistanceFn (distance/distance.go:85-94): distances between bit codes,
+ * for the binary quantizer only.  Every entry point that takes a float metric rejects them (SDB_ERR_INVALID). */
+#define SDB_METRIC_HAMMING 3
+#define SDB_METRIC_JACCARD 4
 
 #define SDB_MEM_HOST 0
 #define SDB_MEM_DEVICE 1
@@ -58,6 +62,7 @@ typedef enum {
 
 typedef struct sdb_index sdb_index;
 typedef struct sdb_pq sdb_pq;
+typedef struct sdb_bq sdb_bq;
 
 const char *sdb_last_error(void);
 int sdb_abi_version(void);
@@ -585,6 +590,57 @@ int sdb_index_union_prune(sdb_index *ix, uint64_t id, uint64_t m, const uint64_t
  * once, not per graph version, and could not be rolled back with it. */
 int sdb_index_set_codes(sdb_index *ix, uint64_t n, const uint64_t *ids, const uint8_t *codes);
 int sdb_index_get_codes(const sdb_index *ix, uint64_t n, const uint64_t *ids, uint8_t *codes);
+
+/* ---------------------------------------------------------------------------------------------
+ * shard/vectorstore/binary.go + the bit distances of distance/distance.go
+ * ------------------------------------------------------------------------------------------- */
+/* newBinaryQuantizer (binary.go:36-64) without its bucket: bit_metric is SDB_METRIC_HAMMING or SDB_METRIC_JACCARD
+ * (distance.GetBitDistanceFn, distance.go:85-94), dim 1..4096.  A code is W = ceil(dim / 64) uint64 words
+ * (binary.go:107-111).  The quantizer starts without a threshold. */
+int sdb_bq_create(uint32_t dim, uint32_t bit_metric, int device, sdb_bq **out);
+int sdb_bq_destroy(sdb_bq *bq);
+/* The threshold, one float per element: params.Threshold replicated by the caller (binary.go:51-56) or the
+ * _binaryQuantizerThreshold entry of a bucket (:58-61).  thr[dim] follows `mem`; the call blocks.  SDB_ERR_STATE once
+ * the quantizer has been attached to an index: the stored codes were cut at the threshold it has. */
+int sdb_bq_set_threshold(sdb_bq *bq, const float *thr, int mem);
+/* What Flush writes under _binaryQuantizerThreshold (binary.go:236-244): *is_set = 0 and thr untouched for a
+ * quantizer without a threshold (the reference's nil slice).  thr[dim] is host memory and may be NULL. */
+int sdb_bq_get_threshold(const sdb_bq *bq, float *thr, int *is_set);
+/* binaryQuantizer.Fit, first pass (binary.go:152-173): per element one float32 sum over the n rows of X[n][dim], one
+ * addition per row in the order given (the reference visits its items in Go-map order: unspecified), then one float32
+ * division by float32(n).  A quantizer that already has a threshold is left as it is (:148).  The TriggerThreshold
+ * policy stays with the caller.  X follows `mem`. */
+int sdb_bq_fit(sdb_bq *bq, const float *X, uint64_t n, int mem, void *stream);
+/* binaryQuantizer.encode (binary.go:103-129) for n vectors: bit i % 64 of codes[v][i / 64] is set iff
+ * vectors[v][i] > thr[i] -- strictly, so never for a NaN; the bits past dim are 0.  codes[n][W].  SDB_ERR_STATE for a
+ * quantizer without a threshold (encode returns nil, :104-106). */
+int sdb_bq_encode(const sdb_bq *bq, const float *vectors, uint64_t n, uint64_t *codes, int mem, void *stream);
+/* distance.BitDistFunc as obtained from GetBitDistanceFn (distance.go:12,85-94), batched over codes of W words:
+ * out[q*nc + c] = hammingDistance (distance.go:45-54: float32 of the population count of x ^ y) or jaccardDistance
+ * (:56-67: 1 - float32(|x & y|) / float32(|x | y|), one float32 division and one subtraction; 0 when the union is
+ * empty) of qcodes[q] and ccodes[c].  W 1..64, nq at most 65535 per call (SDB_ERR_INVALID beyond).  Buffers follow
+ * `mem`. */
+int sdb_bit_distance_batch(int bit_metric, uint32_t W, const uint64_t *qcodes, uint64_t nq, const uint64_t *ccodes,
+                           uint64_t nc, float *out, int mem, int device, void *stream);
+/* Switch an index to the binary quantizer (a maintenance call like sdb_index_attach_pq).  A quantizer without a
+ * threshold is fitted first, as binaryQuantizer.Fit does over its items (binary.go:145-185): from the index's live
+ * committed rows in storage order -- the start node included, it is a stored point (vamana.go:93-120 -> vecStore.Set);
+ * tombstones skipped -- and keeps that threshold (sdb_bq_get_threshold).  Whether enough points are stored
+ * (TriggerThreshold, :148) is the caller's decision.  Every stored row is then encoded (Fit's second pass, :176-180 /
+ * Set, :131-139) into [rows][W] words in HBM.  From then on searches (sdb_index_search_batch, _bitmap,
+ * sdb_cluster_search_batch, sdb_index_flat_search, sdb_index_distance_batch) evaluate bitDistFn(encode(query), code)
+ * (DistanceFromFloat, :187-200) and inserts / deletes / prunes bitDistFn(code, code) (DistanceFromPoint, :213-223); ids,
+ * visit order, counters and trace follow from those distances by the same rules as before.  The float32 rows stay in
+ * HBM.  SDB_ERR_STATE with a product or another binary quantizer attached or a write transaction open,
+ * SDB_ERR_INVALID when dim or device differ.  The index keeps `bq` and reads its threshold in every search and insert:
+ * the quantizer must outlive the index (destroy the index first).  A call that fails leaves both as they were, the
+ * quantizer unfitted if it came unfitted. */
+int sdb_index_attach_bq(sdb_index *ix, sdb_bq *bq, void *stream);
+/* What a bucket holds under NodeKey(id, 'q') for a binary store (binaryQuantizedPoint.ReadFrom / WriteTo,
+ * binary.go:275-310): ids [n] u64, codes [n][W] u64, host memory, on an index with an attached binary quantizer.  The
+ * rules of sdb_index_set_codes: unknown id SDB_ERR_NOT_FOUND and nothing written, not inside a write transaction. */
+int sdb_index_set_bit_codes(sdb_index *ix, uint64_t n, const uint64_t *ids, const uint64_t *codes);
+int sdb_index_get_bit_codes(const sdb_index *ix, uint64_t n, const uint64_t *ids, uint64_t *codes);
 
 #ifdef __cplusplus
 }

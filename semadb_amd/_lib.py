@@ -13,6 +13,7 @@ SO_PATH = os.environ.get("SEMADB_AMD_LIB") or os.path.join(_HERE, "libsemadb_amd
 SDB_OK = 0
 MEM_HOST, MEM_DEVICE = 0, 1
 METRICS = {"euclidean": 0, "cosine": 1, "dot": 2}
+BIT_METRICS = {"hamming": 3, "jaccard": 4}  # distance.GetBitDistanceFn (distance.go:85-94)
 STARTID = 1
 
 f32p = C.POINTER(C.c_float)
@@ -121,6 +122,17 @@ SIGNATURES = {
     "sdb_index_union_prune": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]),
     "sdb_index_set_codes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "sdb_index_get_codes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "sdb_bq_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "sdb_bq_destroy": (C.c_int, [C.c_void_p]),
+    "sdb_bq_set_threshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "sdb_bq_get_threshold": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "sdb_bq_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "sdb_bq_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]),
+    "sdb_bit_distance_batch": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sdb_index_attach_bq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdb_index_set_bit_codes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "sdb_index_get_bit_codes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
 }
 
 

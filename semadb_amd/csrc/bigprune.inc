@@ -97,10 +97,10 @@ template <int NG, bool L2, class Want, class Emit>
 __device__ __forceinline__ void big_chunk(const BuildArgs &a, uint32_t x, const uint32_t *slots, uint32_t n, uint32_t j0,
                                           float *qs, int lane, Want want, Emit emit) {
   constexpr int U = NG >= 0 ? ChunkPairs<NG, false>::value : 4;
-  if constexpr (NG == kQuantized) {  // one candidate per lane, table lookups
+  if constexpr (is_quantized(NG)) {  // one candidate per lane, table lookups / population counts
     const uint8_t *cx = a.pq_codes + (size_t)x * a.pq_M;
     const uint32_t j = j0 + lane;
-    if (j < n && want(j)) emit(j, pq_sym_dist(a, cx, a.pq_codes + (size_t)slots[j] * a.pq_M));
+    if (j < n && want(j)) emit(j, code_pair_dist<NG>(a, cx, a.pq_codes + (size_t)slots[j] * a.pq_M));
   } else {
     const int L = lane & 31;
     // any work in this chunk?
@@ -149,7 +149,7 @@ __device__ __forceinline__ void big_chunk(const BuildArgs &a, uint32_t x, const 
 
 template <int NG>
 static constexpr uint32_t big_chunk_rows() {
-  return NG == kQuantized ? 64 : 2 * (NG >= 0 ? ChunkPairs<NG, false>::value : 4);
+  return is_quantized(NG) ? 64 : 2 * (NG >= 0 ? ChunkPairs<NG, false>::value : 4);
 }
 
 // the distances from B that no cache had

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "bq.h"
 #include "pq.h"
 #include "search_kernel.h"
 
@@ -44,6 +45,7 @@ struct BuildArgs {
   uint64_t *keys_in;   // [nnew*64] (target slot << 32 | a_idx << 6 | edge position)
   uint64_t *keys_sorted;
   // quantized store (NG == kQuantized): point-to-point distances are sums over the centroid-pair table
+  // bit codes (NG == kBitHamming / kBitJaccard): pq_codes holds the [n][W] 64-bit words, pq_M = 8 W bytes per row
   const uint8_t *pq_codes;  // [n][M]
   const float *pq_cdists;   // [M][K][K]
   uint32_t pq_M, pq_K;
@@ -110,6 +112,23 @@ __device__ __forceinline__ float pq_sym_dist(const BuildArgs &a, const uint8_t *
   float dist = 0.0f;
   for (uint32_t i = 0; i < a.pq_M; i++) dist += a.pq_cdists[((size_t)i * a.pq_K + cx[i]) * a.pq_K + cy[i]];
   return dist;
+}
+
+// Binary quantizer (binary.go:213-223): DistanceFromPoint is the bit distance of two code rows.  The two kinds take
+// every branch the product quantizer's kind takes -- one candidate per lane, no float-row tiling, no cached or tabled
+// pair distances -- with their own pair function.
+constexpr int kBitHamming = -3, kBitJaccard = -4;
+constexpr bool is_quantized(int NG) { return NG <= kQuantized; }
+
+// DistanceFromPoint between two code rows of a quantized store
+template <int NG>
+__device__ __forceinline__ float code_pair_dist(const BuildArgs &a, const uint8_t *__restrict__ cx,
+                                                const uint8_t *__restrict__ cy) {
+  if constexpr (NG == kQuantized) {
+    return pq_sym_dist(a, cx, cy);
+  } else {
+    return bit_pair_dist<NG == kBitJaccard>(reinterpret_cast<const uint64_t *>(cx), reinterpret_cast<const uint64_t *>(cy), a.pq_M / 8);
+  }
 }
 
 constexpr uint64_t kNoKey = ~0ull;
@@ -354,14 +373,14 @@ __device__ void robust_prune_wave(const BuildArgs &a, uint32_t self_slot, int nc
       i = found + 1;
       continue;
     }
-    if constexpr (NG == kQuantized) {  // one candidate per lane: M table lookups each
+    if constexpr (is_quantized(NG)) {  // one candidate per lane: M table lookups each
       const uint8_t *cp = a.pq_codes + (size_t)p * a.pq_M;
       for (int base = (found + 1) & ~63; base < nc; base += 64) {
         const int j = base + lane;
         const bool lv = j > found && j < nc && !(s_rem[j] & 1u);
         ev += (uint32_t)__popcll(__ballot(lv));
         if (lv) {
-          const float d = pq_sym_dist(a, cp, a.pq_codes + (size_t)s_slot[j] * a.pq_M);
+          const float d = code_pair_dist<NG>(a, cp, a.pq_codes + (size_t)s_slot[j] * a.pq_M);
           if (a.alpha * d < s_dist[j]) s_rem[j] |= 1u;  // :132
         }
       }
@@ -465,9 +484,9 @@ struct PruneLds {
 // product.go:279-305).  Callers have synchronised after filling in_slot; synchronises before returning.
 template <int NG, bool L2>
 __device__ void dists_from_point(const BuildArgs &a, uint32_t point, uint32_t nc, const PruneLds &l, int lane) {
-  if constexpr (NG == kQuantized) {
+  if constexpr (is_quantized(NG)) {
     const uint8_t *cp = a.pq_codes + (size_t)point * a.pq_M;
-    for (uint32_t c = lane; c < nc; c += 64) l.in_dist[c] = pq_sym_dist(a, cp, a.pq_codes + (size_t)l.in_slot[c] * a.pq_M);
+    for (uint32_t c = lane; c < nc; c += 64) l.in_dist[c] = code_pair_dist<NG>(a, cp, a.pq_codes + (size_t)l.in_slot[c] * a.pq_M);
   } else {
     constexpr int U = NG >= 0 ? ChunkPairs<NG, false>::value : 4;
     const int L = lane & 31;
@@ -529,7 +548,7 @@ __global__ __launch_bounds__(64) void k_prune_new(const BuildArgs a) {
   __syncthreads();
   uint32_t n_eval = 0;
   robust_prune_wave<NG, L2>(a, self, (int)nc, l.in_slot, l.in_dist, l.s_slot, l.s_dist, l.s_rem, l.qs, lane, nullptr, 0,
-                            NG != kQuantized, &n_eval);
+                            !is_quantized(NG), &n_eval);
   stat_add(a, kStPrunePairs, n_eval, lane);
   const uint32_t nb = a.adj[(size_t)self * kAdjStride + lane];  // this lane wrote it
   a.keys_in[(size_t)q * 64 + lane] =
@@ -976,14 +995,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NG == 24 ? 1
     }
     // B overflows: distances from B (distFn = DistanceFromPoint(nB) :49) to its neighbours and the t new points
     const int nc = (int)deg + (int)t;
-    if constexpr (NG == kQuantized) {
+    if constexpr (is_quantized(NG)) {
       __syncthreads();
       for (int c = lane; c < nc; c += 64)
         l.in_slot[c] = c >= (int)deg ? req_slot(done + (size_t)(c - (int)deg)) : kNoSlot;
       if (lane < (int)deg) l.in_slot[lane] = row;
       __syncthreads();
       const uint8_t *cb = a.pq_codes + (size_t)b * a.pq_M;
-      for (int c = lane; c < nc; c += 64) l.in_dist[c] = pq_sym_dist(a, cb, a.pq_codes + (size_t)l.in_slot[c] * a.pq_M);
+      for (int c = lane; c < nc; c += 64) l.in_dist[c] = code_pair_dist<NG>(a, cb, a.pq_codes + (size_t)l.in_slot[c] * a.pq_M);
     } else {
       // candidate c: c < deg -> row entry c (edge order), then the new points in insert order (:55-56; Add
       // dedupes, and a new node can not already be a neighbour).  Cached distances are taken as they are;
@@ -1263,6 +1282,8 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
   const RowLayout &l = ix->lay;
   const uint32_t n0 = ix->n;
   const sdb_pq *pq = ix->pq;
+  const sdb_bq *bq = ix->bq;
+  const bool quant = pq || bq;  // the quantized kinds: no float-row tiling, no distance tables
   struct Cleanup {
     std::vector<void *> ptrs;
     hipStream_t s;
@@ -1371,7 +1392,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
   // the tiled prune's pair tables, handed from its all-pairs phase to the selection kernel (64 KB per point of a round)
   float *pair_tab = nullptr, *pair_dists = nullptr;
   uint32_t *pair_slots = nullptr;
-  if (!pq && ix->tune_no_tile != 3) {
+  if (!quant && ix->tune_no_tile != 3) {
     SDB_HIP(hipMalloc(&pair_tab, (size_t)max_round * kTileMaxCand * kTileMaxCand * 4));
     cleanup.ptrs.push_back(pair_tab);
     SDB_HIP(hipMalloc(&pair_slots, (size_t)max_round * kTileMaxCand * 4));
@@ -1383,7 +1404,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
   uint32_t *def_words = nullptr, *def_slots = nullptr;
   float *def_dists = nullptr;
   const uint32_t def_cap = 2 * max_round + 64;
-  if (!pq) {
+  if (!quant) {
     SDB_HIP(hipMalloc(&def_words, ((size_t)3 * def_cap + 4) * 4));  // [count, pad x3][self][nc][done]
     cleanup.ptrs.push_back(def_words);
     SDB_HIP(hipMalloc(&def_slots, (size_t)def_cap * kTileMaxCand * 4));
@@ -1395,7 +1416,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
   // per new point: the (slot, distance) pairs its search evaluates, direct-mapped (SearchArgs::dcache)
   constexpr uint32_t kDcacheBits = SDB_DCACHE_BITS;  // 8 192 entries = 64 KB per point: ~4 000 evaluations, ~80 % survive
   uint2 *dcache = nullptr;
-  if (!pq) {
+  if (!quant) {
     SDB_HIP(hipMalloc(&dcache, ((size_t)max_round << kDcacheBits) * sizeof(uint2)));
     cleanup.ptrs.push_back(dcache);
   }
@@ -1406,7 +1427,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
   // and quantizer tables of searches that run meanwhile: 4 GB or a sixteenth of the device, whichever is more (at
   // 10M rows the cache is 41 GB; on a device near capacity it used to be taken first and starve the rest).
   float *pairc = nullptr;
-  if (!pq && l.ng <= 6 && n >= 256 && n >= (uint64_t)n0 / 4 && !ix->tune_no_defer) {
+  if (!quant && l.ng <= 6 && n >= 256 && n >= (uint64_t)n0 / 4 && !ix->tune_no_defer) {
     const size_t bytes = (size_t)total_rows * kMaxDirty * 64 * sizeof(float);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
@@ -1465,6 +1486,8 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
   // a fitted quantizer encodes on Set (product.go:161-169); from here on every distance of the insert is a
   // table distance: LUT for the search (DistanceFromFloat), centroid pairs for the prunes (DistanceFromPoint)
   if (pq) SDB_W_TRY(pq_encode_device(pq, dvec, n, ix->d_codes + (size_t)n0 * pq->M, stream));
+  // ... and so does the binary quantizer (binary.go:131-139): the insert's search and prunes read these code rows
+  if (bq) SDB_W_TRY(bq_encode_device(bq->d_thr, l.dim, dvec, n, reinterpret_cast<uint64_t *>(ix->d_codes) + (size_t)n0 * bq->W, stream));
   SDB_W_HIP(hipMemcpyAsync(ix->d_ids + n0, new_ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
   // host-side id bookkeeping of the points of one completed round: h_ids / id2slot / max_node_id move together
   // with ix->n, so that an error return never leaves ids that resolve to slots past the rows in use
@@ -1527,6 +1550,9 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
       sa.pq_lut = lut, sa.pq_codes = ix->d_codes, sa.pq_M = pq->M, sa.pq_K = pq->K;
       sa.pq_lut_in_lds = (lut_row <= 64 * 1024) ? 1u : 0u;
     }
+    if (bq)
+      sa.bq_codes = reinterpret_cast<const uint64_t *>(ix->d_codes), sa.bq_thr = bq->d_thr, sa.bq_W = bq->W,
+      sa.bq_metric = (uint32_t)bq->metric;
     if (!search_uses_hash(sa, rs)) SDB_W_HIP(hipMemsetAsync(bitsets, 0, (size_t)rs * words * 4, stream));
     SDB_W_TRY(launch_greedy_search(sa, rs, stream));  // read-only on the graph: a failure here adds nothing to what the rounds before it did
     // ---- robustPrune + back-edges
@@ -1539,6 +1565,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     ba.vis_slots = vis_slots, ba.vis_dists = vis_dists, ba.vis_count = vis_count, ba.vis_cap = vis_cap;
     ba.keys_in = keys_in, ba.keys_sorted = keys_sorted;
     if (pq) ba.pq_codes = ix->d_codes, ba.pq_cdists = pq->d_cdists, ba.pq_M = pq->M, ba.pq_K = pq->K;
+    if (bq) ba.pq_codes = ix->d_codes, ba.pq_M = ix->code_bytes;
     ba.dcache = dcache, ba.dcache_shift = 32 - kDcacheBits;
     ba.big_count = big_count, ba.big_list = big_list, ba.big_min = big_min, ba.big_cap = big_cap;
     ba.start_slot = (uint32_t)ix->start_slot;
@@ -1553,6 +1580,9 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     bool start_pruned = false;
     in_round = true;
     int rc = pq ? launch_round<kQuantized, false>(ba, stream, sort_tmp, sort_tmp_bytes, end_bit, &big_scratch, &start_pruned)
+         : bq ? (bq->metric == SDB_METRIC_JACCARD
+                     ? launch_round<kBitJaccard, false>(ba, stream, sort_tmp, sort_tmp_bytes, end_bit, &big_scratch, &start_pruned)
+                     : launch_round<kBitHamming, false>(ba, stream, sort_tmp, sort_tmp_bytes, end_bit, &big_scratch, &start_pruned))
          : ix->P.metric == SDB_METRIC_EUCLIDEAN
              ? launch_round_ng<true>(ba, stream, sort_tmp, sort_tmp_bytes, end_bit, &big_scratch, &start_pruned)
              : launch_round_ng<false>(ba, stream, sort_tmp, sort_tmp_bytes, end_bit, &big_scratch, &start_pruned);

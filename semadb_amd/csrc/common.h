@@ -86,6 +86,35 @@ struct RowLayout {
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// host/device staging helper: returns a device pointer for `p` (copying when it is host memory)
+struct Staged {
+  void *dev = nullptr;
+  void *owned = nullptr;
+  void *host_dst = nullptr;
+  size_t bytes = 0;
+  ~Staged() {
+    if (owned) (void)hipFree(owned);
+  }
+};
+
+inline int stage_in(Staged &s, const void *p, size_t bytes, int mem, hipStream_t stream, bool copy = true) {
+  s.bytes = bytes;
+  if (mem == SDB_MEM_DEVICE) {
+    s.dev = const_cast<void *>(p);
+    return SDB_OK;
+  }
+  SDB_HIP(hipMalloc(&s.owned, bytes ? bytes : 16));
+  s.dev = s.owned;
+  s.host_dst = const_cast<void *>(p);
+  if (copy && bytes) SDB_HIP(hipMemcpyAsync(s.dev, p, bytes, hipMemcpyHostToDevice, stream));
+  return SDB_OK;
+}
+
+inline int stage_out(Staged &s, hipStream_t stream) {
+  if (s.owned && s.host_dst && s.bytes) SDB_HIP(hipMemcpyAsync(s.host_dst, s.dev, s.bytes, hipMemcpyDeviceToHost, stream));
+  return SDB_OK;
+}
+
 // hipFuncSetAttribute applies to the function on the CURRENT device: a process that drives several GPUs
 // (sdb_cluster_create_local) has to set a kernel's attribute once per device, not once per process.
 inline bool first_use_on_this_device(std::atomic<uint64_t> &seen) {

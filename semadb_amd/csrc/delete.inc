@@ -236,6 +236,9 @@ template <class Fill>
 static int big_prune_any(const sdb_index *ix, const BuildArgs &a, uint32_t node, uint32_t nc, BigScratch &sc,
                          hipStream_t stream, Fill fill, bool take_all = false) {
   if (ix->pq) return big_prune<kQuantized, false>(a, node, nc, sc, stream, fill, take_all);
+  if (ix->bq)
+    return ix->bq->metric == SDB_METRIC_JACCARD ? big_prune<kBitJaccard, false>(a, node, nc, sc, stream, fill, take_all)
+                                                : big_prune<kBitHamming, false>(a, node, nc, sc, stream, fill, take_all);
   const bool l2 = ix->P.metric == SDB_METRIC_EUCLIDEAN;
 #define SDB_BIG_CASE(NGV) \
   case NGV: return l2 ? big_prune<NGV, true>(a, node, nc, sc, stream, fill, take_all) : big_prune<NGV, false>(a, node, nc, sc, stream, fill, take_all);
@@ -313,6 +316,8 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
   a.b.dirty = ix->d_dirty, a.b.no_tile = ix->tune_no_tile ? 1u : 0u;  // the test knob of the build's tiled prune switches this one too
   const sdb_pq *pq = ix->pq;  // fitted quantizer: DistanceFromPoint is the centroid-pair sum (product.go:296-304)
   if (pq) a.b.pq_codes = ix->d_codes, a.b.pq_cdists = pq->d_cdists, a.b.pq_M = pq->M, a.b.pq_K = pq->K;
+  const sdb_bq *bq = ix->bq;  // binary quantizer: the bit distance of two code rows (binary.go:213-223)
+  if (bq) a.b.pq_codes = ix->d_codes, a.b.pq_M = ix->code_bytes;
   a.ids = ix->d_ids, a.del = d_flags, a.has_inbound = d_flags + N, a.to_prune = d_flags + 2 * (size_t)N, a.n = N;
   uint32_t *d_bound = nullptr;
   SDB_HIP(hipMalloc(&d_bound, (size_t)N * 4));
@@ -400,6 +405,8 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
       a.cap = kTierCap[tier];
       first += cnt;
       int rc = pq ? launch_delete<kQuantized, false>(a, (uint32_t)cnt, stream)
+           : bq ? (bq->metric == SDB_METRIC_JACCARD ? launch_delete<kBitJaccard, false>(a, (uint32_t)cnt, stream)
+                                                    : launch_delete<kBitHamming, false>(a, (uint32_t)cnt, stream))
            : ix->P.metric == SDB_METRIC_EUCLIDEAN ? launch_delete_ng<true>(a, (uint32_t)cnt, stream)
                                                   : launch_delete_ng<false>(a, (uint32_t)cnt, stream);
       if (rc != SDB_OK) return rc;
@@ -603,6 +610,8 @@ extern "C" int sdb_index_union_prune(sdb_index *ix, uint64_t id, uint64_t m, con
   a.metric = (int)ix->P.metric, a.alpha = ix->P.alpha, a.R = ix->P.degree_bound;
   const sdb_pq *pq = ix->pq;
   if (pq) a.pq_codes = ix->d_codes, a.pq_cdists = pq->d_cdists, a.pq_M = pq->M, a.pq_K = pq->K;
+  const sdb_bq *bq = ix->bq;
+  if (bq) a.pq_codes = ix->d_codes, a.pq_M = ix->code_bytes;
   uint32_t *d_extra = nullptr;
   SDB_HIP(hipMalloc(&d_extra, (extra.size() + 1) * 4));
   struct Free {
@@ -622,6 +631,8 @@ extern "C" int sdb_index_union_prune(sdb_index *ix, uint64_t id, uint64_t m, con
   try {
   if (!chip_wide) {
     rc = pq ? launch_union<kQuantized, false>(a, node, d_extra, me, stream)
+         : bq ? (bq->metric == SDB_METRIC_JACCARD ? launch_union<kBitJaccard, false>(a, node, d_extra, me, stream)
+                                                  : launch_union<kBitHamming, false>(a, node, d_extra, me, stream))
          : ix->P.metric == SDB_METRIC_EUCLIDEAN ? launch_union_ng<true>(a, node, d_extra, me, stream)
                                                 : launch_union_ng<false>(a, node, d_extra, me, stream);
   } else {

@@ -7,6 +7,7 @@
 // assembly's order (dist_core.h), so every distance is bit-identical to the reference's.
 #include <cfloat>
 
+#include "bq.h"
 #include "search_kernel.h"
 
 namespace sdb {
@@ -91,6 +92,23 @@ __global__ __launch_bounds__(64) void k_index_distance(const float *__restrict__
   for (int u = 0; u < U; u++)
     if (L == 0 && cidx[u] < nc)  // unknown point -> math.MaxFloat32 (plain.go:78-82)
       out[(size_t)q * nc + cidx[u]] = known[u] ? metric_finish(res[u], metric) : FLT_MAX;
+}
+
+// ---- bit codes by slot: binaryQuantizer.DistanceFromFloat (binary.go:187-200) batched; one lane per candidate ------
+template <bool JACCARD>
+__global__ __launch_bounds__(256) void k_index_bit_distance(const uint64_t *__restrict__ qcodes,
+                                                            const uint64_t *__restrict__ codes,
+                                                            const uint32_t *__restrict__ slots, float *__restrict__ out,
+                                                            uint64_t nc, uint32_t W) {
+  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t q = blockIdx.y;
+  if (c >= nc) return;
+  const uint32_t slot = slots[(size_t)q * nc + c];
+  if (slot == kNoSlot) {  // unknown point -> math.MaxFloat32 (binary.go:194-198)
+    out[(size_t)q * nc + c] = FLT_MAX;
+    return;
+  }
+  out[(size_t)q * nc + c] = bit_pair_dist<JACCARD>(qcodes + (size_t)q * W, codes + (size_t)slot * W, W);
 }
 
 }  // namespace sdb
@@ -200,13 +218,24 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
   hipError_t e = hipMemcpyAsync(dslots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, stream);
   const float *q = queries;
   float *o = out;
+  const sdb_bq *bq = ix->bq;  // attached binary quantizer: bitDistFn(encode(query), code[slot])
+  uint64_t *dqc = nullptr;
+  if (e == hipSuccess && bq) e = hipMalloc(&dqc, nq * bq->W * 8);
   if (e == hipSuccess && mem == SDB_MEM_HOST) {
     e = hipMalloc(&dq, nq * l.dim * 4);
     if (e == hipSuccess) e = hipMalloc(&dout, nq * nc * 4);
     if (e == hipSuccess) e = hipMemcpyAsync(dq, queries, nq * l.dim * 4, hipMemcpyHostToDevice, stream);
     q = dq, o = dout;
   }
-  if (e == hipSuccess) {
+  if (e == hipSuccess && bq) {
+    if (bq_encode_device(bq->d_thr, l.dim, q, nq, dqc, stream) != SDB_OK) e = hipErrorLaunchFailure;
+    const dim3 grid((unsigned)((nc + 255) / 256), (unsigned)nq);
+    if (e == hipSuccess && bq->metric == SDB_METRIC_JACCARD)
+      hipLaunchKernelGGL(k_index_bit_distance<true>, grid, dim3(256), 0, stream, dqc, (const uint64_t *)ix->d_codes, dslots, o, nc, bq->W);
+    else if (e == hipSuccess)
+      hipLaunchKernelGGL(k_index_bit_distance<false>, grid, dim3(256), 0, stream, dqc, (const uint64_t *)ix->d_codes, dslots, o, nc, bq->W);
+    if (e == hipSuccess) e = hipGetLastError();
+  } else if (e == hipSuccess) {
     dim3 grid((unsigned)((nc + 7) / 8), (unsigned)nq);
     size_t lds = (size_t)(l.ng * 128 + 32) * sizeof(float);
     if (ix->P.metric == SDB_METRIC_EUCLIDEAN)
@@ -222,6 +251,7 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
   if (e == hipSuccess) e = hipStreamSynchronize(stream);  // dslots is freed below
   (void)hipFree(dslots);
   if (dq) (void)hipFree(dq);
+  if (dqc) (void)hipFree(dqc);
   if (dout) (void)hipFree(dout);
   if (e != hipSuccess) return fail(SDB_ERR_DEVICE, "index_distance_batch failed: %s", hipGetErrorString(e));
   return SDB_OK;

@@ -21,6 +21,7 @@
 #define SDB_SCAN_PAIRS 1
 #endif
 
+#include "bq.h"
 #include "pq.h"
 #include "search_kernel.h"
 
@@ -101,6 +102,27 @@ __global__ __launch_bounds__(256) void k_flat_dist_pq(const float *__restrict__ 
   float dist = 0.0f;
   for (uint32_t i = 0; i < M; i++) dist += l[i * K + cd[i]];
   out[(size_t)q * out_stride + c] = dist;
+}
+
+// The same block for a binary-quantized store: bitDistFn(encode(query), code[slot]) (binary.go:191-200), one lane per
+// stored row, the query's W words at a wave-uniform address.  qcodes [nq][W] come from the encode kernel (bq.hip).
+template <bool JACCARD>
+__global__ __launch_bounds__(256) void k_flat_dist_bq(const uint64_t *__restrict__ qcodes, const uint64_t *__restrict__ codes,
+                                                      const uint32_t *__restrict__ slots,
+                                                      const uint32_t *__restrict__ slot_off, uint32_t first_row,
+                                                      uint32_t rows, float *__restrict__ out, uint32_t out_stride,
+                                                      uint32_t W) {
+  const uint32_t q = blockIdx.y;
+  uint32_t nrows = rows;
+  const uint32_t *myslots = nullptr;
+  if (slots) {
+    myslots = slots + slot_off[q];
+    nrows = slot_off[q + 1] - slot_off[q];
+  }
+  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= nrows) return;
+  const uint32_t slot = myslots ? myslots[c] : first_row + c;
+  out[(size_t)q * out_stride + c] = bit_pair_dist<JACCARD>(qcodes + (size_t)q * W, codes + (size_t)slot * W, W);
 }
 
 // ---- phase 2: fold a distance block into the running top list (flat.go:98-124), one wave per query -------
@@ -692,7 +714,7 @@ extern "C" int sdb_index_flat_search(sdb_index *ix, uint64_t nq, const float *qu
   // must fit LDS), euclidean rows -- and the others when the matrix-core scan is switched off -- of up to 608 floats
   // on the packed-FMA kernel (k_flat_scan).  The first rows still go through the block path: they seed the thresholds.
   constexpr uint32_t kSeedRows = 4096, kMinSegment = 32768, kCandCap = 8192;
-  const bool streamable = !filtered && !ix->pq && l.nblk >= 1 && n >= kMinSegment && nq <= 8192;
+  const bool streamable = !filtered && !ix->pq && !ix->bq && l.nblk >= 1 && n >= kMinSegment && nq <= 8192;
   const bool mfma = streamable && ix->P.metric != SDB_METRIC_EUCLIDEAN && l.nblk <= 4 * kMfmaMaxGroups && !ix->tune_no_mfma &&
                     flat_mfma_lds_bytes(l.nblk, l.tail, nq) <= 160 * 1024;
   const bool fast = mfma || (streamable && l.tail == 0 && l.nblk <= 19);
@@ -712,6 +734,8 @@ extern "C" int sdb_index_flat_search(sdb_index *ix, uint64_t nq, const float *qu
   const size_t o_d = carve((size_t)nq * stride * 4);
   const sdb_pq *pq = ix->pq;
   const size_t o_lut = carve(pq ? (size_t)nq * pq->M * pq->K * 4 : 0);
+  const sdb_bq *bq = ix->bq;
+  const size_t o_qc = carve(bq ? (size_t)nq * bq->W * 8 : 0);  // the queries' codes
   const size_t o_thr = carve(fast ? nq * 4 : 0);
   const size_t o_cnt = carve(fast ? nq * 4 + 256 : 0), o_cand = carve(fast ? (size_t)nq * kCandCap * 8 : 0);
   const uint32_t qsw_floats = mfma ? (uint32_t)((nq + 15) / 16) * (l.nblk * 512 + (l.tail ? kTailImgFloats : 0)) : 0;
@@ -772,6 +796,16 @@ extern "C" int sdb_index_flat_search(sdb_index *ix, uint64_t nq, const float *qu
       if (first == 0) SDB_TRY(pq_build_lut(pq, dq, nq, (float *)(buf + o_lut), stream));
       hipLaunchKernelGGL(k_flat_dist_pq, dim3((rows + 255) / 256, (unsigned)nq), dim3(256), 0, stream,
                          (const float *)(buf + o_lut), ix->d_codes, d_fs, d_fo, first, rows, d_dist, stride, pq->M, pq->K);
+    } else if (bq) {
+      uint64_t *qc = (uint64_t *)(buf + o_qc);
+      if (first == 0) SDB_TRY(bq_encode_device(bq->d_thr, l.dim, dq, nq, qc, stream));
+      const dim3 g((rows + 255) / 256, (unsigned)nq);
+      if (bq->metric == SDB_METRIC_JACCARD)
+        hipLaunchKernelGGL(k_flat_dist_bq<true>, g, dim3(256), 0, stream, qc, (const uint64_t *)ix->d_codes, d_fs, d_fo, first,
+                           rows, d_dist, stride, bq->W);
+      else
+        hipLaunchKernelGGL(k_flat_dist_bq<false>, g, dim3(256), 0, stream, qc, (const uint64_t *)ix->d_codes, d_fs, d_fo, first,
+                           rows, d_dist, stride, bq->W);
     } else if (ix->P.metric == SDB_METRIC_EUCLIDEAN)
       hipLaunchKernelGGL(k_flat_dist<true>, grid, dim3(256), lds, stream, ix->d_slab, dq, d_fs, d_fo, first, rows, d_dist,
                          stride, l.dim, l.nblk, l.ng, l.tail, l.ld, (int)ix->P.metric);
@@ -1014,6 +1048,7 @@ extern "C" int sdb_index_set_vectors(sdb_index *ix, uint64_t n, const uint64_t *
     dvec = staging;
   }
   int rc = store_rows_public(ix, n0, (uint32_t)n, dvec, nullptr);
+  if (rc == SDB_OK && ix->bq) rc = encode_bit_rows_public(ix, n0, (uint32_t)n, nullptr);  // Set encodes (binary.go:131-139)
   hipError_t e = hipMemcpy(ix->d_ids + n0, new_ids.data(), n * 8, hipMemcpyHostToDevice);
   (void)hipDeviceSynchronize();
   if (staging) (void)hipFree(staging);

@@ -87,6 +87,12 @@ struct sdb_index {
   // product quantizer attachment (product.go): codes per slot + tables
   const sdb_pq *pq = nullptr;
   uint8_t *d_codes = nullptr;
+  // binary quantizer attachment (binary.go): d_codes then holds [cap][W] uint64 words, the BinaryVector of every
+  // stored point (start node included), and travels wherever product codes do (growth, compaction).  At most one of
+  // pq / bq is set.  code_bytes: bytes of one row of d_codes (M, or 8 W; 0 without a quantizer).
+  const sdb_bq *bq = nullptr;
+  uint32_t code_bytes = 0;
+  bool quantized() const { return pq != nullptr || bq != nullptr; }
   // Quantizers of up to kAdjCodesMaxM sub-vectors: every node's neighbours' code rows once more, BEHIND ITS ADJACENCY
   // ROW -- [cap][kAdjStride][M] bytes, entry e = the code row of edge e -- the way the reference keeps a node's
   // neighbours as cached point objects (node.go:37-54 LoadNeighbours: one fetch gives ids and codes).  A hop of the

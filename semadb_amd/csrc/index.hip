@@ -6,6 +6,7 @@
 #include <new>
 #include <stdexcept>
 
+#include "bq.h"
 #include "pq.h"
 #include "search_kernel.h"
 
@@ -455,6 +456,7 @@ bool search_uses_hash(const SearchArgs &a, uint32_t nq) {
   // quantized store: only with the small LUT of M*K <= 2048 entries next to the table (M = 32's 32 KB LUT leaves
   // room for three walks per CU beside the 16 KB table: 0.95 M QPS against 1.31 M on the bitset at five)
   if (a.pq_codes) return pq_wide_shape(a) >= 0 || (a.pq_lut_in_lds && (size_t)a.pq_M * a.pq_K <= 2048);
+  if (a.bq_codes) return true;  // bit codes: the query is 512 bytes of LDS beside the table
   switch (a.ng) {
     case 0: case 1: case 2: case 3: case 4: case 6: case 8: case 12: case 16: case 24: return true;
     default: return false;
@@ -521,7 +523,7 @@ constexpr int kWideWaves = SDB_WIDE_WAVES;
 static bool wide_walk(const SearchArgs &a, uint32_t nq) {
   // (the build's warm-up rounds come here too -- rounds of up to 512 points while the graph is small, ~330 of a 1M
   // build's ~580 rounds: their visit logs and distance tables are written by the walker like any other wave's)
-  if (a.wide_mode == 1 || a.pq_codes || !search_uses_hash(a, nq)) return false;
+  if (a.wide_mode == 1 || a.pq_codes || a.bq_codes || !search_uses_hash(a, nq)) return false;
   // 257 .. 512 queries (eight waves per query): faster than one wave per query for rows of up to 384 floats only
   // (d = 384: 0.56 against 0.65 ms; 512: 0.98 against 0.78; 768: 1.20 against 1.05; profiles/r05_latency.json)
   return a.wide_mode == 2 || nq <= (a.ng <= 3 ? 2 : 1) * kWideMaxQueries;
@@ -558,7 +560,7 @@ static int launch_wide(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
 // to the bitset kernel: the LDS sets spill to the query's bitsets by themselves (HashVisited::spill clears the bitset
 // first), so such a call needs no bitset cleared ahead either (sketch_walk() is asked by the launcher and by the clear).
 bool sketch_walk(const SearchArgs &a, uint32_t nq) {
-  if (!a.sketch || a.pq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
+  if (!a.sketch || a.pq_codes || a.bq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
   if (!(a.ng == 1 || a.ng == 2 || a.ng == 3 || a.ng == 4 || a.ng == 6)) return false;
   if (wide_walk(a, nq)) return false;
   return search_uses_hash(a, nq) || (a.filt_off && !a.prefer_bitset);
@@ -604,12 +606,29 @@ static int launch_ng(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
   }
 }
 
+// Bit codes (search_kernel.h BitDist): the one-wave walk with every visited-set policy the product one-wave walk has --
+// the 16-bit-cell LDS set for tables of up to 2^24 rows, the 32-bit-cell one beyond, the HBM bitset (SDB_TUNE_NO_HASH,
+// searchSize > 96) -- plain and filtered.  No multi-wave, two-precision or small-call variant.
+template <bool JACCARD>
+static int launch_bits(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
+  using D = BitDist<JACCARD>;
+  if (search_uses_hash(a, nq)) {
+    if ((uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash) return launch_nreg<D, kHash16>(a, nq, stream, D::kLdsBytes);
+    return launch_nreg<D, kHashCapPQ>(a, nq, stream, D::kLdsBytes);
+  }
+  return launch_nreg<D, 0>(a, nq, stream, D::kLdsBytes);
+}
+
 int launch_greedy_search(const SearchArgs &a_in, uint32_t nq, hipStream_t stream) {
   if (nq == 0) return SDB_OK;
   SearchArgs a = a_in;
   if (a.hash_limit == 0 || a.hash_limit > kHashLimit) a.hash_limit = kHashLimit;
   if (a.search_size == 0 || a.search_size > 512)
     return fail(SDB_ERR_INVALID, "searchSize %u not supported on device (1..512)", a.search_size);
+  if (a.bq_codes) {  // binary quantizer with a threshold attached (binary.go:191-200)
+    if (a.bq_metric == SDB_METRIC_JACCARD) return launch_bits<true>(a, nq, stream);
+    return launch_bits<false>(a, nq, stream);
+  }
   if (a.pq_codes) {  // fitted product quantizer attached (product.go:250-277)
     switch (pq_wide_shape(a)) {  // tables too large to sit beside a one-wave walk: one query per four waves
       case 1: return a.pq_narrow == 2 ? launch_pqw<32, 0>(a, nq, stream) : launch_pqw<15, 17>(a, nq, stream);  // two per CU
@@ -706,7 +725,7 @@ int sdb_index::reserve(uint32_t rows) {
     SDB_TRY(fresh.get((void **)&ndirty, (size_t)ncap));
     SDB_TRY(fresh.get((void **)&nad, (size_t)ncap * kAdjStride * sizeof(float)));  // edge-distance cache of the write path (index.h)
     SDB_TRY(fresh.get((void **)&ndc, (size_t)ncap * sizeof(uint32_t)));
-    if (pq) SDB_TRY(fresh.get((void **)&ncodes, (size_t)ncap * pq->M));  // the code rows of a quantized store grow with it
+    if (code_bytes) SDB_TRY(fresh.get((void **)&ncodes, (size_t)ncap * code_bytes));  // the code rows of a quantized store grow with it
     return SDB_OK;
   };
   if (int rc = get_required()) {
@@ -771,7 +790,7 @@ int sdb_index::reserve(uint32_t rows) {
   if (n) {
     SDB_HIP(hipMemcpy(nad, d_adjdist, (size_t)n * kAdjStride * sizeof(float), hipMemcpyDeviceToDevice));
     SDB_HIP(hipMemcpy(ndc, d_dcount, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    if (pq) SDB_HIP(hipMemcpy(ncodes, d_codes, (size_t)n * pq->M, hipMemcpyDeviceToDevice));
+    if (code_bytes) SDB_HIP(hipMemcpy(ncodes, d_codes, (size_t)n * code_bytes, hipMemcpyDeviceToDevice));
     if (ac_row) {
       SDB_HIP(hipMemcpy(nacw, d_adjcodes, (size_t)n * ac_row, hipMemcpyDeviceToDevice));
       SDB_HIP(hipMemcpy(nacr, r_adjcodes, (size_t)n * ac_row, hipMemcpyDeviceToDevice));
@@ -783,11 +802,11 @@ int sdb_index::reserve(uint32_t rows) {
     for (void *p : {(void *)d_slab, (void *)d_adj, (void *)r_adj, (void *)d_deg, (void *)d_clean, (void *)d_ids,
                     (void *)r_ids, (void *)d_dirty, (void *)d_adjdist, (void *)d_dcount})
       if (p) (void)hipFree(p);
-    if (pq && d_codes) (void)hipFree(d_codes);
+    if (code_bytes && d_codes) (void)hipFree(d_codes);
     if (had_ac) (void)hipFree(d_adjcodes), (void)hipFree(r_adjcodes), d_adjcodes = nacw, r_adjcodes = nacr;  // (NULL: dropped)
     d_slab = nslab, d_adj = nadj, r_adj = nradj, d_deg = ndeg, d_clean = nclean, d_ids = nids, r_ids = nrids;
     d_dirty = ndirty, d_adjdist = nad, d_dcount = ndc;
-    if (pq) d_codes = ncodes;
+    if (code_bytes) d_codes = ncodes;
     fresh.keep = true;
     cap = ncap;
     view.adj = r_adj, view.ids = r_ids, view.adj_codes = r_adjcodes;
@@ -916,7 +935,7 @@ __global__ __launch_bounds__(256) void k_sketch_rows(const float *__restrict__ s
 }  // namespace sdb
 
 bool sdb_index::sketch_supported() const {
-  if (lay.tail != 0 || pq) return false;
+  if (lay.tail != 0 || pq || bq) return false;
   return lay.ng == 1 || lay.ng == 2 || lay.ng == 3 || lay.ng == 4 || lay.ng == 6;
 }
 
@@ -1459,6 +1478,10 @@ static int store_rows(sdb_index *ix, uint32_t first, uint32_t n, const float *ve
   return SDB_OK;
 }
 
+// binaryQuantizer.Set (binary.go:131-139) for slab rows [first, first + n) of an index with a binary quantizer attached
+static int encode_bit_rows(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream) {
+  return bq_encode_slab(ix->bq->d_thr, ix->lay, ix->d_slab, first, n, reinterpret_cast<uint64_t *>(ix->d_codes), stream);
+}
 int sdb_index_set_start(sdb_index *ix, const float *vec, int mem) try {
   if (!ix || !vec) return fail(SDB_ERR_INVALID, "NULL argument");
   if (ix->start_slot >= 0) return SDB_OK;  // vamana.go:95-97: already there
@@ -1466,6 +1489,7 @@ int sdb_index_set_start(sdb_index *ix, const float *vec, int mem) try {
   DeviceGuard dg(ix->P.device);
   SDB_TRY(ix->reserve(1));
   SDB_TRY(store_rows(ix, 0, 1, vec, mem, nullptr));
+  if (ix->bq) SDB_TRY(encode_bit_rows(ix, 0, 1, nullptr));  // vecStore.Set encodes (binary.go:131-139)
   uint64_t id = SDB_STARTID;
   SDB_HIP(hipMemcpy(ix->d_ids, &id, sizeof(id), hipMemcpyHostToDevice));
   SDB_HIP(hipDeviceSynchronize());
@@ -1565,6 +1589,7 @@ int sdb_index_load(sdb_index *ix, uint64_t n, const uint64_t *ids, const float *
   SDB_HIP(hipMemcpy(ix->d_deg, deg.data(), deg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   SDB_HIP(hipMemcpy(ix->d_ids, ix->h_ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
   SDB_TRY(store_rows(ix, 0, (uint32_t)n, vectors, mem, nullptr));
+  if (ix->bq) SDB_TRY(encode_bit_rows(ix, 0, (uint32_t)n, nullptr));
   SDB_TRY(ix->publish_full());
   undo.keep = true;
   return SDB_OK;
@@ -1947,6 +1972,9 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
 
   const uint32_t vcap = trace ? trace->visit_cap : 0;
   auto launch = [&]() -> int {
+    if (ix->bq)  // DistanceFromFloat encodes the query once (binary.go:192): the walk does, when it starts (BitDist::init)
+      a.bq_codes = reinterpret_cast<const uint64_t *>(ix->d_codes), a.bq_thr = ix->bq->d_thr, a.bq_W = ix->bq->W,
+      a.bq_metric = (uint32_t)ix->bq->metric;
     if (ix->pq) {  // fitted quantizer: DistanceFromFloat builds the M x K table first (product.go:255-263)
       const sdb_pq *pq = ix->pq;
       SDB_TRY(ws->ensure_lut((size_t)nq * pq->M * pq->K * sizeof(float)));
@@ -1991,7 +2019,7 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
   const bool zc_out = zc_ok && device_view_of_host(out_ids, nq * limit * sizeof(uint64_t), &z_i) &&
                       device_view_of_host(out_dists, nq * limit * sizeof(float), &z_d) &&
                       device_view_of_host(out_counts, nq * sizeof(uint32_t), &z_c);
-  const bool zc_q = zc_ok && !ix->pq && device_view_of_host(queries, nq * l.dim * sizeof(float), &z_q);
+  const bool zc_q = zc_ok && !ix->pq && !ix->bq && device_view_of_host(queries, nq * l.dim * sizeof(float), &z_q);
   if (zc_out && zc_q) {
     a.queries = static_cast<const float *>(z_q);
     a.out_ids = static_cast<uint64_t *>(z_i), a.out_dists = static_cast<float *>(z_d), a.out_counts = static_cast<uint32_t *>(z_c);
@@ -2283,7 +2311,7 @@ int sdb_index_size_in_memory(const sdb_index *ix, int64_t *bytes) try {
   // vecStore.SizeInMemory + nodeStore.SizeInMemory (vamana.go:83-85), as held in HBM
   // slab row + adjacency row + its distance cache + degree / clean / cached counters + id (+ code row)
   // (+ the second adjacency / id copy of the graph versions, + the neighbours' code rows behind both adjacency copies)
-  *bytes = (int64_t)ix->cap * (ix->lay.ld * 4 + 3 * kAdjStride * 4 + 3 * 4 + 2 * 8 + (ix->pq ? ix->pq->M : 0) +
+  *bytes = (int64_t)ix->cap * (ix->lay.ld * 4 + 3 * kAdjStride * 4 + 3 * 4 + 2 * 8 + ix->code_bytes +
                                (ix->has_adjcodes() ? 2 * kAdjStride * ix->pq->M : 0)) +
            (int64_t)ix->sketch_cap * (ix->lay.ld * 2 + 4);  // (+ the float16 copy of the rows and their norms, SDB_TUNE_SKETCH)
   return SDB_OK;
@@ -2323,7 +2351,7 @@ int sdb_index_compact(sdb_index *ix) try {
   std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);  // searches wait: every buffer they read is replaced
   SDB_HIP(hipDeviceSynchronize());
   const uint32_t n = ix->n, cap = ix->cap, ld = ix->lay.ld;
-  const uint32_t M = ix->pq ? ix->pq->M : 0;
+  const uint32_t M = ix->code_bytes;  // bytes of a code row (product or bit codes)
   std::vector<uint32_t> map(n, kNoSlot), live;
   live.reserve(n - ix->n_dead);
   for (uint32_t s = 0; s < n; s++)
@@ -2512,6 +2540,9 @@ SDB_API_CATCH("sdb_index_export")
 }  // extern "C"
 
 namespace sdb {
+int encode_bit_rows_public(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream) {
+  return encode_bit_rows(ix, first, n, stream);
+}
 int store_rows_public(sdb_index *ix, uint32_t first, uint32_t n, const float *dev_vectors, hipStream_t stream) {
   return store_rows(ix, first, n, dev_vectors, SDB_MEM_DEVICE, stream);
 }
@@ -2552,6 +2583,7 @@ extern "C" int sdb_index_attach_pq(sdb_index *ix, const sdb_pq *pq, void *stream
     const int want = ix->P.metric == SDB_METRIC_COSINE ? SDB_METRIC_EUCLIDEAN : (int)ix->P.metric;
     if (pq->metric != want) return fail(SDB_ERR_INVALID, "quantizer metric does not match the index metric");
   }
+  if (ix->bq) return fail(SDB_ERR_STATE, "a binary quantizer is attached");
   if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open");
   DeviceGuard dg(ix->P.device);
   hipStream_t stream = as_stream(stream_);
@@ -2585,6 +2617,7 @@ extern "C" int sdb_index_attach_pq(sdb_index *ix, const sdb_pq *pq, void *stream
   if (ix->d_codes) (void)hipFree(ix->d_codes);
   ix->d_codes = ncodes;
   ix->pq = pq;
+  ix->code_bytes = pq->M;
   ix->drop_sketch();  // a quantized walk has no use for the float16 copy (sketch_supported)
   // the neighbours' code rows behind the adjacency rows, for the new codes (M <= 32; index.h d_adjcodes)
   SDB_TRY(ix->alloc_adjcodes());
@@ -2642,3 +2675,92 @@ extern "C" int sdb_index_get_codes(const sdb_index *ix, uint64_t n, const uint64
   return SDB_OK;
 }
 SDB_API_CATCH("sdb_index_get_codes")
+
+// binaryQuantizer with a threshold (binary.go:131-139, 187-234): every stored point's BinaryVector in HBM, searches on
+// bitDistFn(encode(query), code), prunes on bitDistFn(code, code).  Without a threshold the quantizer is fitted first
+// (Fit, :145-185) from the index's own rows.
+extern "C" int sdb_index_attach_bq(sdb_index *ix, sdb_bq *bq, void *stream_) try {
+  if (!ix || !bq) return fail(SDB_ERR_INVALID, "NULL argument");
+  if (bq->dim != ix->lay.dim) return fail(SDB_ERR_INVALID, "quantizer dim %u != index dim %u", bq->dim, ix->lay.dim);
+  if (bq->device != ix->P.device) return fail(SDB_ERR_INVALID, "quantizer and index live on different devices");
+  if (ix->broken) return fail(SDB_ERR_STATE, "index is unusable after a failed write; reload it from the bucket");
+  if (ix->pq) return fail(SDB_ERR_STATE, "a product quantizer is attached");
+  if (ix->bq) return fail(SDB_ERR_STATE, "a binary quantizer is attached");
+  if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open");
+  if (!bq->has_thr && ix->n == ix->n_dead) return fail(SDB_ERR_STATE, "quantizer has no threshold and the index no rows to fit it from");
+  DeviceGuard dg(ix->P.device);
+  hipStream_t stream = as_stream(stream_);
+  // like attach_pq: the code rows are written into a buffer of their own while searches go on in full precision, then
+  // (quantizer, codes) change hands under the exclusive lock
+  const bool fitted_here = !bq->has_thr;
+  if (fitted_here) {  // Fit's first pass over the items in storage order, tombstones skipped (outside a transaction the writer's ids are the committed ones)
+    SDB_TRY(bq_fit_slab(ix->lay, ix->d_slab, ix->d_ids, ix->n, bq->d_thr, stream));
+    SDB_HIP(hipStreamSynchronize(stream));
+    bq->has_thr = true;
+  }
+  uint64_t *ncodes = nullptr;
+  hipError_t me = hipMalloc(&ncodes, (size_t)ix->cap * bq->W * 8);
+  int rc = me == hipSuccess ? bq_encode_slab(bq->d_thr, ix->lay, ix->d_slab, 0, ix->n, ncodes, stream)  // Fit's second pass / Set
+                            : fail(SDB_ERR_DEVICE, "hipMalloc failed: %s", hipGetErrorString(me));
+  (void)hipStreamSynchronize(stream);
+  if (rc != SDB_OK) {  // nothing changes hands: a quantizer fitted by this call is unfitted again
+    if (ncodes) (void)hipFree(ncodes);
+    if (fitted_here) bq->has_thr = false;
+    return rc;
+  }
+  std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
+  (void)hipDeviceSynchronize();  // walks launched on the float rows
+  ix->d_codes = reinterpret_cast<uint8_t *>(ncodes);
+  ix->bq = bq;
+  bq->attached = true;
+  ix->code_bytes = bq->W * 8;
+  ix->drop_sketch();  // a bit-code walk has no use for the float16 copy (sketch_supported)
+  return forget_prune_state(ix);
+}
+SDB_API_CATCH("sdb_index_attach_bq")
+
+// What a bucket holds under NodeKey(id, 'q') for a binary store (binaryQuantizedPoint.ReadFrom / WriteTo,
+// binary.go:275-310): ids [n], codes [n][W] u64, host memory.  The rules of sdb_index_set_codes.
+extern "C" int sdb_index_set_bit_codes(sdb_index *ix, uint64_t n, const uint64_t *ids, const uint64_t *codes) try {
+  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
+  if (!ix->bq) return fail(SDB_ERR_STATE, "no binary quantizer attached");
+  if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open: codes are set outside it");
+  if (n == 0) return SDB_OK;
+  if (!ids || !codes) return fail(SDB_ERR_INVALID, "NULL argument");
+  const size_t B = ix->code_bytes;
+  DeviceGuard dg(ix->P.device);
+  for (uint64_t i = 0; i < n; i++)  // nothing is written unless every id resolves
+    if (ix->slot_of(ids[i]) < 0) return fail(SDB_ERR_NOT_FOUND, "point %llu not found", (unsigned long long)ids[i]);
+  std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
+  SDB_HIP(hipDeviceSynchronize());
+  uint64_t i = 0;
+  while (i < n) {
+    const int64_t s0 = ix->slot_of(ids[i]);
+    uint64_t j = i + 1;
+    while (j < n && ix->slot_of(ids[j]) == s0 + (int64_t)(j - i)) j++;
+    SDB_HIP(hipMemcpy(ix->d_codes + (size_t)s0 * B, reinterpret_cast<const uint8_t *>(codes) + i * B, (j - i) * B, hipMemcpyHostToDevice));
+    i = j;
+  }
+  return forget_prune_state(ix);
+}
+SDB_API_CATCH("sdb_index_set_bit_codes")
+
+extern "C" int sdb_index_get_bit_codes(const sdb_index *ix, uint64_t n, const uint64_t *ids, uint64_t *codes) try {
+  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
+  if (!ix->bq) return fail(SDB_ERR_STATE, "no binary quantizer attached");
+  if (n == 0) return SDB_OK;
+  if (!ids || !codes) return fail(SDB_ERR_INVALID, "NULL argument");
+  const size_t B = ix->code_bytes;
+  DeviceGuard dg(ix->P.device);
+  uint64_t i = 0;
+  while (i < n) {
+    const int64_t s0 = ix->slot_of(ids[i]);
+    if (s0 < 0) return fail(SDB_ERR_NOT_FOUND, "point %llu not found", (unsigned long long)ids[i]);
+    uint64_t j = i + 1;
+    while (j < n && ix->slot_of(ids[j]) == s0 + (int64_t)(j - i)) j++;
+    SDB_HIP(hipMemcpy(reinterpret_cast<uint8_t *>(codes) + i * B, ix->d_codes + (size_t)s0 * B, (j - i) * B, hipMemcpyDeviceToHost));
+    i = j;
+  }
+  return SDB_OK;
+}
+SDB_API_CATCH("sdb_index_get_bit_codes")

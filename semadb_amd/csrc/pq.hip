@@ -929,35 +929,6 @@ static int pq_fill_cdists(sdb_pq *pq, hipStream_t stream) {
   return SDB_OK;
 }
 
-// host/device staging helper: returns a device pointer for `p` (copying when it is host memory)
-struct Staged {
-  void *dev = nullptr;
-  void *owned = nullptr;
-  void *host_dst = nullptr;
-  size_t bytes = 0;
-  ~Staged() {
-    if (owned) (void)hipFree(owned);
-  }
-};
-
-static int stage_in(Staged &s, const void *p, size_t bytes, int mem, hipStream_t stream, bool copy = true) {
-  s.bytes = bytes;
-  if (mem == SDB_MEM_DEVICE) {
-    s.dev = const_cast<void *>(p);
-    return SDB_OK;
-  }
-  SDB_HIP(hipMalloc(&s.owned, bytes ? bytes : 16));
-  s.dev = s.owned;
-  s.host_dst = const_cast<void *>(p);
-  if (copy && bytes) SDB_HIP(hipMemcpyAsync(s.dev, p, bytes, hipMemcpyHostToDevice, stream));
-  return SDB_OK;
-}
-
-static int stage_out(Staged &s, hipStream_t stream) {
-  if (s.owned && s.host_dst && s.bytes) SDB_HIP(hipMemcpyAsync(s.host_dst, s.dev, s.bytes, hipMemcpyDeviceToHost, stream));
-  return SDB_OK;
-}
-
 }  // namespace sdb
 
 using namespace sdb;

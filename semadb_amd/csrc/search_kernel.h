@@ -18,6 +18,7 @@
 //     for instruction count: the reduce tree is DPP adds (dist_core.h), row slots reach the lanes
 //     through a rank-compacted LDS list, a row address is one 64-bit mad (PlainDist::hop_fast).
 #pragma once
+#include "bq.h"
 #include "dist_core.h"
 #include "index.h"
 
@@ -92,6 +93,11 @@ struct SearchArgs {
   float sk_emax, sk_ymax;            // max over the rows of ||y - y16|| and of ||y16|| (k_sketch_rows), rounded up
   uint32_t sk_audit;                 // != 0: evaluate everything exactly as well and count decisions the exact distance contradicts
   unsigned long long *sk_counters;   // [0] += neighbours discarded on their float16 distance, [1] += contradicted ones (audit)
+  // binary-quantized store (binary.go:187-200): per-slot codes [n][W] of 64-bit words, the threshold [dim] the walk
+  // encodes its query with, and the bit metric (SDB_METRIC_HAMMING / SDB_METRIC_JACCARD); bq_codes == NULL: none
+  const uint64_t *bq_codes;
+  const float *bq_thr;
+  uint32_t bq_W, bq_metric;
 };
 
 // pairs of candidate rows a wave keeps in flight per chunk.  DEEP (one wave per SIMD, the batch-search
@@ -1078,6 +1084,48 @@ struct PQDist {
     dist += lut[6 * K + ((pre.y >> 16) & 0xFF)];
     dist += lut[7 * K + (pre.y >> 24)];
     return dist;
+  }
+};
+
+// Binary quantizer with a threshold: dist = bitDistFn(encode(query), code[slot]) (binary.go:191-200), hammingDistance
+// or jaccardDistance of distance.go:45-67 -- integer population counts, one conversion (hamming) or one float32
+// division and one subtraction (jaccard).  One lane per neighbour, like PQDist: the lane reads its W-word code row by
+// slot (16-byte loads when W is even: rows are 8 W bytes from a 256-byte-aligned base), the query's words -- encoded
+// once by init, the wave's ballots (binary.go:123-127) -- are read from LDS at a wave-uniform address.
+template <bool JACCARD>
+struct BitDist {
+  static constexpr bool kSpeculate = false;
+  static constexpr bool kHasStamps = false;
+  static constexpr bool kPointDistances = false;  // (the build's distance table is a full-precision store's)
+  static constexpr size_t kLdsBytes = 64 * sizeof(uint64_t) + 8;  // W <= 64 query words, on an 8-byte boundary
+  const uint64_t *xq;  // LDS [W]
+  uint32_t W;
+  __device__ __forceinline__ void init(const SearchArgs &a, uint32_t q, int lane, float *lds) {
+    uint64_t *w = reinterpret_cast<uint64_t *>((reinterpret_cast<uintptr_t>(lds) + 7) & ~(uintptr_t)7);
+    const float *v = a.queries + (size_t)q * a.dim;
+    W = a.bq_W;
+    for (uint32_t k = 0; k < W; k++) {
+      const uint32_t i = k * 64 + (uint32_t)lane;
+      const bool bit = i < a.dim && v[i] > a.bq_thr[i];  // strict: never for a NaN; bits past dim stay 0
+      const uint64_t word = __ballot(bit);
+      if (lane == 0) w[k] = word;
+    }
+    wave_lds_sync();
+    xq = w;
+  }
+  __device__ __forceinline__ float row_dist(const SearchArgs &a, uint32_t slot) const {
+    const uint64_t *__restrict__ y = a.bq_codes + (size_t)slot * W;
+    return (W & 1u) == 0 ? bit_pair_dist<JACCARD, true>(xq, y, W) : bit_pair_dist<JACCARD, false>(xq, y, W);
+  }
+  __device__ __forceinline__ float one(const SearchArgs &a, uint32_t s, int) { return row_dist(a, s); }
+  __device__ __forceinline__ void speculation(bool, const uint32_t *) {}
+  __device__ __forceinline__ void ahead(const SearchArgs &, const uint32_t *, int, bool) {}
+  __device__ __forceinline__ void skip(int) {}
+  __device__ __forceinline__ void begin_row(const SearchArgs &, const uint32_t *, int) {}
+  __device__ __forceinline__ void prefetch(const SearchArgs &, uint32_t, bool) {}
+  __device__ __forceinline__ float hop(const SearchArgs &a, uint32_t nb, uint64_t pend, int lane) {
+    if (!((pend >> lane) & 1ull)) return 0.0f;
+    return row_dist(a, nb);
   }
 };
 

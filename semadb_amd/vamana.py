@@ -101,10 +101,11 @@ class IndexVamana:
         if params.DistanceMetric not in METRICS:
             raise SemaDBError(1, "unknown distance metric %s" % params.DistanceMetric)
         self.name, self.parameters, self.device = name, params, device
-        # vectorstore.New (vamana.go:64): None = plain store (the slab); a ProductQuantizer waits for Fit
+        # vectorstore.New (vamana.go:64): None = plain store (the slab); a ProductQuantizer / BinaryQuantizer waits for Fit
         from . import vectorstore
         self._store = vectorstore.New(getattr(params, "Quantizer", None), params.DistanceMetric, params.VectorSize, device)
         self._pq = None
+        self._bq = None
         self._fit_rng = np.random.default_rng(fit_seed)
         self.last_fit_first_idx = None
         p = IndexParams(params.VectorSize, METRICS[params.DistanceMetric], params.SearchSize, params.DegreeBound,
@@ -119,6 +120,10 @@ class IndexVamana:
             self.set_tuning("sketch", self._forced_sketch)
             if os.environ.get("SEMADB_AMD_TEST_WIDE_WALK"):  # ... and the batch walk (which has the stage) for small calls too
                 self.set_tuning("wide_walk", int(os.environ["SEMADB_AMD_TEST_WIDE_WALK"]))
+        # a binary store with a given threshold encodes from the first Set on (binary.go:51-56, 131-139): the start node
+        # and the first batch's graph are already built on bit distances.  Without one, Fit attaches it later.
+        if isinstance(self._store, vectorstore.BinaryQuantizer) and self._store.threshold() is not None:
+            vectorstore.attach_binary(self, self._store)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -296,12 +301,19 @@ class IndexVamana:
         vectors in storage order (the reference walks a Go map), first centroid drawn at random
         (kmeans.go:61-63); the labels become the points' centroid ids (:216-218)."""
         pq = self._store
+        from . import vectorstore
+        if isinstance(pq, vectorstore.BinaryQuantizer):
+            # binaryQuantizer.Fit (binary.go:145-185): a given threshold was attached at construction; otherwise the
+            # column means once TriggerThreshold points are stored (:148)
+            if self._bq is not None or self.stats()[0] < pq.params.TriggerThreshold:
+                return False
+            vectorstore.attach_binary(self, pq)
+            return True
         if pq is None or self._pq is not None:
             return False
         n = self.stats()[0]
         if n < pq.params.TriggerThreshold:
             return False
-        from . import vectorstore
         ids, vecs, _, _ = self.export()
         first = self._fit_rng.integers(0, n, pq.M)
         self.last_fit_first_idx = first

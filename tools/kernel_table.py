@@ -34,6 +34,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 SGPR_TIMED, SGPR_FILTERED, SGPR_ANY = 64, 128, 160
 TIMED = re.compile(
     r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, false|4, true)>, 2, (false|true), 8192u>"
+    r"|k_greedy_search<sdb::BitDist<(false|true)>, "  # the bit-code walks (tools/bench_bq.py times the hamming one)
     r"|k_greedy_search_wide<(3|6), false, (8|16), (false|true)>"
     r"|k_greedy_search_pq2<|k_greedy_search_pqw<15, 33, 4294967295u, 4, 15, true>"
     r"|k_pq_lut_t<true, 3, 96>|k_pq_lut_t<true, 0, 4>|k_pq_lut_mfma<|k_pq_encode_t<true, 3, true>|k_pq_encode_pair<true, 4>"
