@@ -279,7 +279,15 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
  *                        Ids, distances, visit order and
  *                        counters are the same bits either way.  2: the same, and every discarded neighbour is
  *                        evaluated exactly as well; sdb_index_sketch_stats counts decisions the exact distance
- *                        contradicts (must stay 0).  0: off, the copy is freed.  On (1) by default.  The copy is a
+ *                        contradicts (must stay 0).  0: off, the copy is freed.
+ *                        3: as 1, with an INT8 copy of the rows in place of the float16 one (+ 25 % of the rows' memory
+ *                        instead of + 50 %: y8 = clamp(rint(y / s), -127, 127), one scale s per table) on the tables that
+ *                        have that stage -- cosine / dot, rows of up to 384 floats -- and whose rows quantise well under one
+ *                        scale (a table whose row norms differ widely keeps the float16 copy, and so does a table with
+ *                        SDB_TUNE_SKETCH_FILTERED set, whose filtered hop is the float16 stage's).  Every other table behaves as under 1.  A neighbour the
+ *                        int8 distance does not prove discarded goes straight to its float32 row: same bits again.
+ *                        4: 3 with 2's audit.  A table never holds both copies; setting the knob frees one and builds
+ *                        the other.  3 by default.  The copy is a
  *                        cache: it is taken only when the device keeps max(4 GB, a sixteenth of its memory) free
  *                        afterwards, a table that grows drops it rather than fail, and a device error while building it
  *                        leaves it off (the write itself succeeds); searches then read float32 rows. */
@@ -302,9 +310,9 @@ int sdb_index_distance_batch(sdb_index *ix, uint64_t nq, const float *queries, u
  * measured on the full-size shape (tools/bench_filter.py --sketch measures it). */
 #define SDB_TUNE_SKETCH_FILTERED 14
 int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value);
-/* SDB_TUNE_SKETCH's counters since the knob was last set, filtered calls (SDB_TUNE_SKETCH_FILTERED) included: out[0] = neighbours discarded on their float16 distance,
+/* SDB_TUNE_SKETCH's counters since the knob was last set, filtered calls (SDB_TUNE_SKETCH_FILTERED) included: out[0] = neighbours discarded on their float16 (or int8) distance,
  * out[1] = of those, the ones whose exact distance would have been kept (audit mode only; a non-zero value is a bug),
- * out[2] = 1 when searches currently use the float16 copy (it exists and describes the committed rows), else 0. */
+ * out[2] = 1 when searches currently use the float16 or int8 copy (it exists and describes the committed rows), else 0. */
 int sdb_index_sketch_stats(sdb_index *ix, uint64_t out[3]);
 
 /* Counters of the most recent sdb_index_insert_batch call (the C3 roofline, SURVEY 8d: bytes = sum over inserts

@@ -174,7 +174,25 @@ struct sdb_index {
   // Best-effort: no room for it (build_sketch's headroom rule) or a device error while building it leaves it off and
   // the walk reads float32 rows -- never a failed write.
   bool tune_sketch_filtered = false;  // SDB_TUNE_SKETCH_FILTERED: filtered batch searches take the hop too (opt-in: its speed against the float32 walk is not measured)
-  uint32_t tune_sketch = 1;  // 0 off (the copy is freed), 1 on (default), 2 on + audit (every discarded neighbour is evaluated exactly as well and checked)
+  // 3 / 4: as 1 / 2 with an INT8 copy in place of the float16 one where the table has that stage (sketch8_supported():
+  // cosine / dot, rows of up to 384 floats) and its rows quantise well enough under one scale (kSketch8MaxRatio);
+  // every other table behaves under 3 / 4 exactly as under 1 / 2.  A table never holds both copies.
+  uint32_t tune_sketch = 3;  // 0 off (the copy is freed), 1 on, 2 on + audit (every discarded neighbour is evaluated exactly as well and checked), 3 (default) / 4: see above
+  bool sketch8 = false;      // the copy in d_sketch is the int8 one: rows of ld BYTES, no per-row floats (d_sketch_norm == NULL)
+  bool sketch8_refused = false;  // this table's rows failed kSketch8MaxRatio: it keeps the float16 copy until the knob is set again
+  float sk8_scale = 0.0f;    // the int8 copy's scale s (y8 = clamp(rint(y / s), -127, 127)): the largest |element| seen / 127, rounded up
+  float sk8_amax = 0.0f;     // that largest |element| (carried across appends, never lowered by deletes)
+  float sk8_rel = 0.0f;      // max over the rows with ||y|| > 0 of ||y - s y8|| / ||y||, rounded up: a row far below the table's scale quantises to nothing
+  // Largest E8max / Y8max (= max ||y - s y8|| / max ||s y8||), and largest error of a single row relative to its own norm
+  // (sk8_rel: dot tables whose row norms differ widely have small rows that all quantise to 0 under one scale while the
+  // ratio of the two maxima, both set by the largest rows, stays small), at which a table takes the int8 copy.  The stage pays while
+  // its int8 rows (1.23 d bytes per evaluated neighbour, rows of visited edges included) plus the float32 rows of the kept
+  // and within-margin neighbours (4 d each) stay below the float16 stage's 2.86 d, i.e. while kept + within-margin stays
+  // below 0.41 of the evaluated; DESIGN 4 records the replay that turns that share into this ratio.
+  static constexpr float kSketch8MaxRatio = 0.16f;
+  bool sketch8_supported() const;  // sketch_supported(), cosine / dot, ng 1 .. 3
+  bool sketch8_wanted() const { return tune_sketch >= 3 && !tune_sketch_filtered && !sketch8_refused && sketch8_supported(); }  // (SDB_TUNE_SKETCH_FILTERED: the filtered hop reads the float16 copy)
+  size_t sketch_row_bytes(bool int8) const { return int8 ? (size_t)lay.ld : (size_t)lay.ld * 2; }
   uint16_t *d_sketch = nullptr;
   float *d_sketch_norm = nullptr;  // [sketch_cap] ||y16||^2 per row (the euclidean form of the first stage)
   uint32_t sketch_cap = 0;   // rows d_sketch has room for
@@ -189,6 +207,8 @@ struct sdb_index {
   // (Re)build for the rows as they are (from > 0: only the rows from there on).  `locked`: the caller holds view_mu
   // exclusively.  Never fails: no room or a device error drops the copy.  Off or unsupported: the copy is freed.
   void build_sketch(hipStream_t stream, uint32_t from, bool locked);
+  // one attempt at one kind of copy: 0 = built, 1 = dropped (no room, a device error), 2 = the int8 copy was refused (kSketch8MaxRatio)
+  int build_sketch_kind(hipStream_t stream, uint32_t from, bool locked, std::unique_lock<sdb::ViewMutex> &wl, bool int8);
   void drop_sketch();  // view_mu held exclusively (or no search can run); waits for the walks that may read it
   bool tune_no_defer = false;  // A/B and parity tests: every back-edge re-prune runs in k_backedges (BuildArgs::def_*)
   uint32_t tune_pq_narrow = 0;  // 1: quantized searches never take a multi-wave walk (k_greedy_search_pqw, k_greedy_search_pq2): A/B and parity tests

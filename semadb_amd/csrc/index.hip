@@ -562,6 +562,7 @@ static int launch_wide(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
 bool sketch_walk(const SearchArgs &a, uint32_t nq) {
   if (!a.sketch || a.pq_codes || a.bq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
   if (!(a.ng == 1 || a.ng == 2 || a.ng == 3 || a.ng == 4 || a.ng == 6)) return false;
+  if (a.sk8 && (a.ng > 3 || a.metric == SDB_METRIC_EUCLIDEAN || a.filt_off)) return false;  // (the int8 copy: Int8Dist's tables and calls only)
   if (wide_walk(a, nq)) return false;
   return search_uses_hash(a, nq) || (a.filt_off && !a.prefer_bitset);
 }
@@ -574,6 +575,14 @@ static int launch_plain(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
   if constexpr (NG == 1 || NG == 2 || NG == 3 || NG == 4 || NG == 6)
     if (sketch_walk(a, nq)) {
       // (few float32 rows survive the first stage: four pairs of them in flight per round leave the registers to the float16 rows)
+      if constexpr (!L2 && NG <= 3)
+        if (a.sk8) {  // the int8 first stage (SDB_TUNE_SKETCH = 3, 4): plain calls of cosine / dot tables
+          using Sk8Dist = Int8Dist<NG>;
+          hipLaunchKernelGGL((k_greedy_search<Sk8Dist, 2, false, kHashCap>), dim3(nq), dim3(64),
+                             HashVisited<kHashCap>::kWords * sizeof(uint32_t) + Sk8Dist::kLdsBytes, stream, a);
+          SDB_HIP(hipGetLastError());
+          return SDB_OK;
+        }
       using SkDist = PlainDist<NG, L2, true, 4, true>;
       const size_t lds = HashVisited<kHashCap>::kWords * sizeof(uint32_t) + SkDist::kLdsBytes;
       if (a.filt_off)  // all three filter forms; the threshold is search_kernel.h list_tail_bound
@@ -756,17 +765,19 @@ int sdb_index::reserve(uint32_t rows) {
   uint16_t *nsk = nullptr;
   float *nskn = nullptr;
   if (sk_keep && sketch_cap < ncap) {
-    const size_t rows_b = (size_t)ncap * lay.ld * sizeof(uint16_t), norm_b = (size_t)ncap * sizeof(float);
+    // (the int8 copy: rows of ld bytes and no per-row floats)
+    const size_t rows_b = (size_t)ncap * sketch_row_bytes(sketch8), norm_b = sketch8 ? 0 : (size_t)ncap * sizeof(float);
     const uint32_t have = std::min(n, sketch_cap);
-    if (!sketch_room(rows_b + norm_b) || hipMalloc(&nsk, rows_b) != hipSuccess || hipMalloc(&nskn, norm_b) != hipSuccess ||
-        (have && (hipMemcpy(nsk, d_sketch, (size_t)have * lay.ld * sizeof(uint16_t), hipMemcpyDeviceToDevice) != hipSuccess ||
-                  hipMemcpy(nskn, d_sketch_norm, (size_t)have * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess))) {
+    if (!sketch_room(rows_b + norm_b) || hipMalloc(&nsk, rows_b) != hipSuccess || (norm_b && hipMalloc(&nskn, norm_b) != hipSuccess) ||
+        (have && (hipMemcpy(nsk, d_sketch, (size_t)have * sketch_row_bytes(sketch8), hipMemcpyDeviceToDevice) != hipSuccess ||
+                  (norm_b && hipMemcpy(nskn, d_sketch_norm, (size_t)have * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)))) {
       (void)hipGetLastError();
       if (nsk) (void)hipFree(nsk);
       if (nskn) (void)hipFree(nskn);
       nsk = nullptr, nskn = nullptr;
     } else {
-      fresh.p.push_back(nsk), fresh.p.push_back(nskn);  // returned with the rest if a step below fails
+      fresh.p.push_back(nsk);  // returned with the rest if a step below fails
+      if (nskn) fresh.p.push_back(nskn);
     }
   }
   // the old buffers are freed below: nothing may still be walking them (searches run on streams of their own)
@@ -812,7 +823,8 @@ int sdb_index::reserve(uint32_t rows) {
     view.adj = r_adj, view.ids = r_ids, view.adj_codes = r_adjcodes;
     view_gen++;
     if (nsk) {
-      (void)hipFree(d_sketch), (void)hipFree(d_sketch_norm);
+      (void)hipFree(d_sketch);
+      if (d_sketch_norm) (void)hipFree(d_sketch_norm);
       d_sketch = nsk, d_sketch_norm = nskn, sketch_cap = ncap;
     }
     if (sk_keep) sketch_gen = view_gen;
@@ -932,7 +944,58 @@ __global__ __launch_bounds__(256) void k_sketch_rows(const float *__restrict__ s
     atomicMax(stats + 1, __float_as_uint(y < 0.0f ? 0.0f : y));
   }
 }
+
+// ---- the int8 copy (SDB_TUNE_SKETCH = 3, 4; search_kernel.h Int8Dist) ----
+// the largest |element| of `count` floats into *out (a NaN's pattern is above every number's)
+__global__ __launch_bounds__(256) void k_sketch8_absmax(const float *__restrict__ v, size_t count, uint32_t *__restrict__ out) {
+  uint32_t m = 0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
+    const uint32_t b = __float_as_uint(fabsf(v[i]));
+    m = b > m ? b : m;
+  }
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t x = (uint32_t)__shfl_xor((int)m, o);
+    m = x > m ? x : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+// one wave per row: y8 = clamp(rint(y / s), -127, 127) (s == 0, a table of zeros: 0), element 128 g + 4 L + k of the row at
+// byte 4 ng L + 4 g + k of the copy's (a lane of the walk reads its 4 ng bytes with one load); the row's ||y - s y8|| and
+// ||s y8||, measured in double and rounded up, into the table-wide maxima stats[0], stats[1], and its error relative to its
+// own norm into stats[3] (rows of zeros have none).  A NaN or Inf in a row makes its figures NaN or infinite, and the
+// maxima with them: the stage then discards nothing (and the table fails kSketch8MaxRatio).
+__global__ __launch_bounds__(256) void k_sketch8_rows(const float *__restrict__ slab, uint8_t *__restrict__ sk, uint32_t n,
+                                                       uint32_t ld, uint32_t ng, float scale, uint32_t *__restrict__ stats) {
+  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const float *s = slab + (size_t)row * ld;
+  uint8_t *d = sk + (size_t)row * ld;
+  double e2 = 0.0, n2 = 0.0, y2 = 0.0;
+  for (uint32_t t = lane; t < ld; t += 64) {
+    const float v = s[t];
+    const float f = scale != 0.0f ? fminf(fmaxf(__builtin_rintf(__fdiv_rn(v, scale)), -127.0f), 127.0f) : 0.0f;
+    const uint32_t g = t >> 7, r = t & 127u;
+    d[(r >> 2) * 4 * ng + g * 4 + (r & 3u)] = (uint8_t)(int8_t)(int)f;
+    const double hv = (double)scale * (double)f, dv = (double)v - hv;
+    e2 += dv * dv, n2 += hv * hv, y2 += (double)v * (double)v;
+  }
+  for (int o = 32; o; o >>= 1) e2 += __shfl_xor(e2, o), n2 += __shfl_xor(n2, o), y2 += __shfl_xor(y2, o);
+  if (lane == 0) {
+    const float e = (float)(sqrt(e2) * 1.0001), y = (float)(sqrt(n2) * 1.0001);  // rounded up past their own rounding
+    atomicMax(stats, __float_as_uint(e < 0.0f ? 0.0f : e));
+    atomicMax(stats + 1, __float_as_uint(y < 0.0f ? 0.0f : y));
+    if (!(y2 == 0.0)) {
+      const float rel = (float)(sqrt(e2 / y2) * 1.0001);
+      atomicMax(stats + 3, __float_as_uint(rel < 0.0f ? 0.0f : rel));
+    }
+  }
+}
 }  // namespace sdb
+
+bool sdb_index::sketch8_supported() const {
+  return sketch_supported() && P.metric != SDB_METRIC_EUCLIDEAN && lay.ng <= 3;
+}
 
 bool sdb_index::sketch_supported() const {
   if (lay.tail != 0 || pq || bq) return false;
@@ -952,7 +1015,7 @@ void sdb_index::drop_sketch() {
   if (d_sketch || d_sketch_norm) (void)hipDeviceSynchronize();  // walks of earlier views may still read it
   if (d_sketch) (void)hipFree(d_sketch);
   if (d_sketch_norm) (void)hipFree(d_sketch_norm);
-  d_sketch = nullptr, d_sketch_norm = nullptr, sketch_cap = 0, sketch_gen = 0;
+  d_sketch = nullptr, d_sketch_norm = nullptr, sketch_cap = 0, sketch_gen = 0, sketch8 = false;
 }
 
 // `from` > 0: the copy is current for rows [0, from) -- a Vamana table never rewrites a committed row, it appends
@@ -969,20 +1032,32 @@ void sdb_index::build_sketch(hipStream_t stream, uint32_t from, bool locked) {
     drop_sketch();
     return;
   }
+  // SDB_TUNE_SKETCH = 3, 4: the int8 copy where the table has that stage; a table whose rows fail kSketch8MaxRatio (now, or
+  // with the rows a later commit appends) frees it and takes the float16 copy from then on
+  if (build_sketch_kind(stream, from, locked, wl, sketch8_wanted()) == 2) {
+    sketch8_refused = true;
+    drop_sketch();
+    (void)build_sketch_kind(stream, 0, locked, wl, false);
+  }
+}
+
+int sdb_index::build_sketch_kind(hipStream_t stream, uint32_t from, bool locked, std::unique_lock<sdb::ViewMutex> &wl, bool int8) {
+  if (d_sketch && sketch8 != int8) drop_sketch();  // the other kind of copy (the knob moved between 1 / 2 and 3 / 4): never both
   const bool carry = from > 0 && from <= n && d_sketch && sketch_cap >= n && sketch_gen != 0;
   if (!carry) from = 0;
   sketch_gen = 0;
-  if (n == 0) return;
+  if (n == 0) return 0;
+  const bool reused = d_sketch != nullptr;
   if (sketch_cap < n) {
     drop_sketch();
-    const size_t rows = (size_t)cap * lay.ld * sizeof(uint16_t), norms = (size_t)cap * sizeof(float);
+    const size_t rows = (size_t)cap * sketch_row_bytes(int8), norms = int8 ? 0 : (size_t)cap * sizeof(float);
     // a cache: without room for it (the rule of build.hip's pair cache) the walk reads float32 rows
-    if (!sketch_room(rows + norms) || hipMalloc(&d_sketch, rows) != hipSuccess || hipMalloc(&d_sketch_norm, norms) != hipSuccess) {
+    if (!sketch_room(rows + norms) || hipMalloc(&d_sketch, rows) != hipSuccess || (norms && hipMalloc(&d_sketch_norm, norms) != hipSuccess)) {
       (void)hipGetLastError();  // (a failed hipMalloc of this cache)
       drop_sketch();
-      return;
+      return 1;
     }
-    sketch_cap = cap;
+    sketch_cap = cap, sketch8 = int8;
   }
   if (!d_sk_counters) {
     if (hipMalloc(&d_sk_counters, 4 * sizeof(unsigned long long)) != hipSuccess ||
@@ -991,33 +1066,68 @@ void sdb_index::build_sketch(hipStream_t stream, uint32_t from, bool locked) {
       if (d_sk_counters) (void)hipFree(d_sk_counters);
       d_sk_counters = nullptr;
       drop_sketch();
-      return;
+      return 1;
     }
   }
   uint16_t *const sk = d_sketch;
   float *const sk_norm = d_sketch_norm;
-  uint32_t *stats = reinterpret_cast<uint32_t *>(d_sk_counters + 2);
-  uint32_t h[2] = {0, 0};
-  if (from) memcpy(&h[0], &sk_emax, 4), memcpy(&h[1], &sk_ymax, 4);
-  const uint32_t rows = n, ld = lay.ld;
+  uint32_t *stats = reinterpret_cast<uint32_t *>(d_sk_counters + 2);  // four words: the two maxima; int8: + the new rows' largest |element|, the largest relative row error
+  uint32_t h[4] = {0, 0, 0, 0};
+  if (from) memcpy(&h[0], &sk_emax, 4), memcpy(&h[1], &sk_ymax, 4), memcpy(&h[3], &sk8_rel, 4);
+  const uint32_t rows = n, ld = lay.ld, ng = lay.ng;
   const float *slab = d_slab;
+  float scale = sk8_scale, amax = sk8_amax;
+  bool ok = true;
+  if (int8) {
+    // The scale: appended rows inside the table's range take the scale the copy has; rows beyond it (and a first build)
+    // set a new one from the largest |element| of ALL rows, and every row is converted again -- one pass over the slab.
+    // Walks of the previous view may still read the copy they were given: they finish before a row of it is rewritten.
+    float newmax = 0.0f;
+    ok = hipMemcpyAsync(stats, h, 16, hipMemcpyHostToDevice, stream) == hipSuccess;
+    if (ok && rows > from) {
+      const size_t count = (size_t)(rows - from) * ld;
+      hipLaunchKernelGGL(sdb::k_sketch8_absmax, dim3((uint32_t)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0, stream,
+                         slab + (size_t)from * ld, count, stats + 2);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(&newmax, stats + 2, 4, hipMemcpyDeviceToHost, stream) == hipSuccess;
+    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
+    if (ok && !(from && newmax <= amax)) {  // (a NaN among the new rows: not inside any range)
+      amax = (!from || newmax > amax || newmax != newmax) ? newmax : amax;
+      const float s0 = amax / 127.0f;
+      scale = (s0 > 0.0f && s0 < 3.0e38f) ? nextafterf(s0, 3.4e38f) : s0;  // rounded up; 0 (a table of zeros), Inf and NaN as they are
+      from = 0, h[0] = h[1] = h[3] = 0;
+      if (reused) ok = hipDeviceSynchronize() == hipSuccess;
+    }
+  }
   if (!locked) wl.unlock();  // (sketch_mu stays held: the knob cannot free the copy under the kernel)
-  bool ok = hipMemcpyAsync(stats, h, 8, hipMemcpyHostToDevice, stream) == hipSuccess;
+  ok = ok && hipMemcpyAsync(stats, h, 16, hipMemcpyHostToDevice, stream) == hipSuccess;
   if (ok && rows > from) {
-    hipLaunchKernelGGL(sdb::k_sketch_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
-                       sk + (size_t)from * ld, sk_norm + from, rows - from, ld, stats);
+    if (int8)
+      hipLaunchKernelGGL(sdb::k_sketch8_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
+                         reinterpret_cast<uint8_t *>(sk) + (size_t)from * ld, rows - from, ld, ng, scale, stats);
+    else
+      hipLaunchKernelGGL(sdb::k_sketch_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
+                         sk + (size_t)from * ld, sk_norm + from, rows - from, ld, stats);
     ok = hipGetLastError() == hipSuccess;
   }
-  ok = ok && hipMemcpyAsync(h, stats, 8, hipMemcpyDeviceToHost, stream) == hipSuccess;
+  ok = ok && hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, stream) == hipSuccess;
   ok = hipStreamSynchronize(stream) == hipSuccess && ok;
   if (!locked) wl.lock();
   if (!ok) {  // best-effort: the write this follows has been published; its searches read float32 rows
     (void)hipGetLastError();
     drop_sketch();
-    return;
+    return 1;
+  }
+  if (int8) {
+    float e, y, rel;
+    memcpy(&e, &h[0], 4), memcpy(&y, &h[1], 4), memcpy(&rel, &h[3], 4);
+    if (!(e <= kSketch8MaxRatio * y) || !(rel <= kSketch8MaxRatio)) return 2;  // (NaN and Inf included)
+    sk8_scale = scale, sk8_amax = amax, sk8_rel = rel;
   }
   memcpy(&sk_emax, &h[0], 4), memcpy(&sk_ymax, &h[1], 4);
   sketch_gen = view_gen;
+  return 0;
 }
 
 int sdb_index::ensure_idmap(const View &vw, hipStream_t stream) const {
@@ -1967,7 +2077,9 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
     if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx &&
         (!filtered || ix->tune_sketch_filtered))  // (filtered calls: opt-in, SDB_TUNE_SKETCH_FILTERED)
       a.sketch = sk, a.sketch_norm = ix->d_sketch_norm, a.sk_emax = ix->sk_emax, a.sk_ymax = ix->sk_ymax,
-      a.sk_audit = knob == 2 ? 1u : 0u, a.sk_counters = ix->d_sk_counters;
+      a.sk_audit = (knob == 2 || knob == 4) ? 1u : 0u, a.sk_counters = ix->d_sk_counters,
+      a.sk8 = ix->sketch8 ? 1u : 0u, a.sk8_scale = ix->sk8_scale;
+    if (a.sk8 && filtered) a.sketch = nullptr, a.sk8 = 0;  // (the int8 stage is the plain calls'; a filtered call reads float32 rows)
   }
 
   const uint32_t vcap = trace ? trace->visit_cap : 0;
@@ -2149,23 +2261,35 @@ int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
       ix->tune_no_zero_copy = value != 0;
       return SDB_OK;
     case SDB_TUNE_SKETCH: {
-      if (value > 2) return fail(SDB_ERR_INVALID, "sketch: 0 = off, 1 = on, 2 = on with audit");
+      if (value > 4) return fail(SDB_ERR_INVALID, "sketch: 0 = off, 1 = float16 copy, 2 = 1 with audit, 3 = int8 copy where the table has one, 4 = 3 with audit");
       DeviceGuard dg(ix->P.device);
       std::lock_guard<std::mutex> sg(ix->sketch_mu);  // a commit converting rows on another thread finishes first
       std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
       SDB_HIP(hipDeviceSynchronize());  // walks that read the copy
       ix->tune_sketch = (uint32_t)value;
+      if (ix->d_sk_counters) SDB_HIP(hipMemset(ix->d_sk_counters, 0, 2 * sizeof(unsigned long long)));  // (every set clears the counters)
       if (!value) {
         ix->drop_sketch();
         return SDB_OK;
       }
-      if (ix->d_sk_counters) SDB_HIP(hipMemset(ix->d_sk_counters, 0, 2 * sizeof(unsigned long long)));
-      if (!ix->in_tx && !ix->sketch_current()) ix->build_sketch(nullptr, 0, true);  // inside a transaction: its commit builds it
+      ix->sketch8_refused = false;  // (a set knob asks again)
+      // inside a transaction: its commit builds it; the other kind of copy than the one held: that one is freed first
+      if (!ix->in_tx && (!ix->sketch_current() || ix->sketch8 != ix->sketch8_wanted())) ix->build_sketch(nullptr, 0, true);
       return SDB_OK;
     }
-    case SDB_TUNE_SKETCH_FILTERED:
+    case SDB_TUNE_SKETCH_FILTERED: {
+      // the filtered hop is the float16 stage's: a table with the opt-in keeps the float16 copy under 3 / 4 too, for
+      // both its walks (sketch8_wanted()); the copy of the other kind is freed and this one built under the knob's locks
+      DeviceGuard dg(ix->P.device);
+      std::lock_guard<std::mutex> sg(ix->sketch_mu);
+      std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
       ix->tune_sketch_filtered = value != 0;
+      if (ix->tune_sketch && !ix->in_tx && ix->d_sketch && ix->sketch8 != ix->sketch8_wanted()) {
+        SDB_HIP(hipDeviceSynchronize());  // walks that read the copy
+        ix->build_sketch(nullptr, 0, true);
+      }
       return SDB_OK;
+    }
     case SDB_TUNE_NO_DEFER:
       ix->tune_no_defer = value != 0;
       return SDB_OK;
@@ -2313,7 +2437,7 @@ int sdb_index_size_in_memory(const sdb_index *ix, int64_t *bytes) try {
   // (+ the second adjacency / id copy of the graph versions, + the neighbours' code rows behind both adjacency copies)
   *bytes = (int64_t)ix->cap * (ix->lay.ld * 4 + 3 * kAdjStride * 4 + 3 * 4 + 2 * 8 + ix->code_bytes +
                                (ix->has_adjcodes() ? 2 * kAdjStride * ix->pq->M : 0)) +
-           (int64_t)ix->sketch_cap * (ix->lay.ld * 2 + 4);  // (+ the float16 copy of the rows and their norms, SDB_TUNE_SKETCH)
+           (int64_t)ix->sketch_cap * (ix->sketch8 ? ix->lay.ld : ix->lay.ld * 2 + 4);  // (+ the float16 copy of the rows and their norms, or the int8 copy, SDB_TUNE_SKETCH)
   return SDB_OK;
 }
 SDB_API_CATCH("sdb_index_size_in_memory")

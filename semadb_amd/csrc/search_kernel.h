@@ -91,6 +91,8 @@ struct SearchArgs {
   const uint16_t *sketch;
   const float *sketch_norm;          // [rows] ||y16||^2 of every row (euclidean tables: d16 = ||q16||^2 + ||y16||^2 - 2 q16.y16)
   float sk_emax, sk_ymax;            // max over the rows of ||y - y16|| and of ||y16|| (k_sketch_rows), rounded up
+  uint32_t sk8;                      // != 0: `sketch` is the INT8 copy (Int8Dist): rows of `ld` bytes, sk_emax / sk_ymax its maxima
+  float sk8_scale;                   // the table's scale s of that copy: y8 = clamp(rint(y / s), -127, 127)
   uint32_t sk_audit;                 // != 0: evaluate everything exactly as well and count decisions the exact distance contradicts
   unsigned long long *sk_counters;   // [0] += neighbours discarded on their float16 distance, [1] += contradicted ones (audit)
   // binary-quantized store (binary.go:187-200): per-slot codes [n][W] of 64-bit words, the threshold [dim] the walk
@@ -693,6 +695,137 @@ struct PlainDist {
       }
     }
     return mydist;
+  }
+};
+
+// The two-precision hop with an INT8 first stage (SDB_TUNE_SKETCH = 3; cosine / dot, rows of 128 .. 384 floats): the
+// index keeps y8 = clamp(rint(y / s), -127, 127) of every row, one scale s per table (index.hip k_sketch8_rows), in
+// place of the float16 copy -- half the bytes of the stage that reads a row for every edge of every hop.  A copy row is
+// ld bytes; lane L's 4 NG bytes of it are contiguous (bytes [4 NG L, 4 NG (L + 1)): group g's elements 4 L .. 4 L + 3
+// at + 4 g), so a lane asks for a row with ONE load of NG dwords where the float16 copy takes NG loads 256 bytes apart.
+//
+// The query becomes two int8 terms once per wave: with s_q = max |q_i| / 127, a = clamp(rint(q / s_q)) and
+// b = clamp(rint((q - s_q a) 128 / s_q)) (the residual of a, |b| <= 64), q^ = (s_q / 128) (128 a + b).  Per row and lane
+// W = (sum a y8 << 7) + sum b y8 from 2 NG v_dot4_i32_i8 -- an exact integer, |W| <= 16 320 x 127 x 384 < 2^31 -- and the
+// 32 sums of a hop go through the transposing butterfly as INTEGER adds: nothing is rounded before the one conversion
+// d8 = metric_finish((s s_q / 128) float(W)), and q^ . y^ = (s s_q / 128) W exactly with y^ = s y8.
+//
+// The bound, as for the float16 stage: q.y - q^.y^ = (q - q^).y^ + q.(y - y^), so |q.y - q^.y^| <= ||q - q^|| Y8max +
+// ||q|| E8max (Cauchy-Schwarz; E8max = max ||y - s y8|| and Y8max = max ||s y8|| measured in double over all rows and
+// rounded up by k_sketch8_rows; ||q - q^|| and ||q|| measured here).  ||q - q^|| is measured against the float32 value
+// of q^_i, one rounding (2^-24 |q^_i|) away from the exact product: 2e-7 ||q|| is added.  The reference's float32 chain
+// and tree round 4 NG + 6 times (2^-24 each, on sums bounded by ||q|| ||y||); d8's scale product, conversion and
+// multiplication three times: below 21 x 2^-24 = 1.3e-6 for NG <= 3, and 2e-5 ||q|| (Y8max + E8max) is charged, the
+// term the float16 stage charges.  Norms are inflated by 1e-4 for their own rounding; the final 1 - dot / -dot and the
+// subtraction of the bound are covered per comparison (sketch_out: 4e-7 of the magnitudes, which also covers a scale
+// product that underflows).  A query or a table with a non-finite element makes the bound infinite or NaN: nothing is
+// discarded then.  A survivor goes straight to the float32 stage (Base::hop): reference order, same bits.
+template <int NG>
+struct Int8Dist : PlainDist<NG, false, true, 4, false> {
+  static_assert(NG >= 1 && NG <= 3, "a hop's 64 int8 rows are held in 32 NG registers");
+  using Base = PlainDist<NG, false, true, 4, false>;
+  static constexpr bool kSketch = true;
+  struct __attribute__((packed, aligned(4))) RowWords { uint32_t w[NG]; };
+  uint32_t qa[NG], qb[NG];  // four int8 each, in xq's element order
+  float sk_eps;             // bound on |d8 - the reference's float32 distance| for this query, any row
+  float sk_scale;           // s s_q / 128
+  uint32_t sky[32][NG];     // pair u: edge 2u (lanes 0..31) and edge 2u + 1 (lanes 32..63)
+  bool sk_go = false, sk_loaded = false;
+
+  __device__ __forceinline__ void init(const SearchArgs &a, uint32_t q, int lane, float *lds) {
+    Base::init(a, q, lane, lds);
+    float mx = 0.0f;
+#pragma unroll
+    for (int g = 0; g < NG; g++)
+      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(this->xq[g].x), fabsf(this->xq[g].y)), fmaxf(fabsf(this->xq[g].z), fabsf(this->xq[g].w))));
+    // (fmaxf drops a NaN: a query with one is caught by the measured error below, which becomes NaN)
+#pragma unroll
+    for (int o = 16; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float sq = mx / 127.0f, inv = sq > 0.0f ? 1.0f / sq : 0.0f, sq128 = sq * 0.0078125f;
+    float e2 = 0.0f, n2 = 0.0f;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+      const float v[4] = {this->xq[g].x, this->xq[g].y, this->xq[g].z, this->xq[g].w};
+      uint32_t pa = 0, pb = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float fa = fminf(fmaxf(__builtin_rintf(v[k] * inv), -127.0f), 127.0f);
+        const float fb = fminf(fmaxf(__builtin_rintf((v[k] - sq * fa) * inv * 128.0f), -127.0f), 127.0f);
+        const float dv = v[k] - sq128 * (fa * 128.0f + fb);  // (128 a + b is exact in float32)
+        e2 = __builtin_fmaf(dv, dv, e2), n2 = __builtin_fmaf(v[k], v[k], n2);
+        pa |= ((uint32_t)(int)fa & 0xFFu) << (8 * k), pb |= ((uint32_t)(int)fb & 0xFFu) << (8 * k);
+      }
+      qa[g] = pa, qb[g] = pb;
+    }
+    // (both halves of the wave hold the same query: the sum over one half's 32 lanes)
+    e2 = rlf(asm_reduce(e2, 0.0f, lane), 0), n2 = rlf(asm_reduce(n2, 0.0f, lane), 0);
+    const float qn = __builtin_sqrtf(n2) * 1.0001f, qerr = __builtin_sqrtf(e2) * 1.0001f + 2e-7f * qn;
+    const SearchArgs &c = cold_args(a);
+    sk_eps = (qerr * c.sk_ymax + qn * c.sk_emax + 2e-5f * qn * (c.sk_ymax + c.sk_emax)) * 1.0001f;
+    sk_scale = c.sk8_scale * sq128;
+  }
+
+  __device__ __forceinline__ bool sketch_go(const SearchArgs &, bool full) const { return full; }
+
+  __device__ __forceinline__ void prefetch(const SearchArgs &a, uint32_t nb, bool valid) {
+    sk_loaded = false;
+    if (!sk_go) return;
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int L = lane & 31;
+    const bool hi = lane >= 32;
+    const char *baseL = reinterpret_cast<const char *>(cold_args(a).sketch) + L * (4 * NG);
+    const uint32_t row_bytes = a.ld;
+    const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
+#pragma unroll
+    for (int u = 0; u < 32; u++) {
+      const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
+      const RowWords r = *reinterpret_cast<const RowWords *>(baseL + (uint64_t)(hi ? s1 : s0) * row_bytes);
+#pragma unroll
+      for (int g = 0; g < NG; g++) sky[u][g] = r.w[g];
+    }
+    sk_loaded = true;
+  }
+
+  // the pending neighbours that AddWithLimit may keep: `out` gets the ones whose int8 distance is above `tail_d` by more
+  // than the bound (every comparison with a NaN is false: such a neighbour is kept for the exact evaluation)
+  __device__ __forceinline__ uint64_t sketch_keep(const SearchArgs &a, uint32_t, uint64_t pend, int lane, float tail_d,
+                                                  uint64_t &out) {
+    out = 0;
+    if (!sk_loaded) return pend;  // (never with the array full: the rows are asked for whenever it is)
+    // one transposing butterfly over the 32 pairs (PlainDist::sketch_keep), on integers
+    int w[32];
+#pragma unroll
+    for (int u = 0; u < 32; u++) {
+      int sa = 0, sb = 0;
+#pragma unroll
+      for (int g = 0; g < NG; g++) {
+        sa = __builtin_amdgcn_sdot4((int)sky[u][g], (int)qa[g], sa, false);
+        sb = __builtin_amdgcn_sdot4((int)sky[u][g], (int)qb[g], sb, false);
+      }
+      w[u] = sa * 128 + sb;
+    }
+#define SDB_SK8_STAGE(S)                                                                 \
+  {                                                                                      \
+    const bool up = (lane & (S)) != 0;                                                   \
+    _Pragma("unroll") for (int i = 0; i < (S); i++) {                                    \
+      const int keep = up ? w[i + (S)] : w[i], send = up ? w[i] : w[i + (S)];            \
+      w[i] = keep + __builtin_amdgcn_ds_swizzle(send, ((S) << 10) | 0x1F);               \
+    }                                                                                    \
+  }
+    SDB_SK8_STAGE(16)
+    SDB_SK8_STAGE(8)
+    SDB_SK8_STAGE(4)
+    SDB_SK8_STAGE(2)
+    SDB_SK8_STAGE(1)
+#undef SDB_SK8_STAGE
+    // lane 32 h + L holds edge 2 L + h: lane j takes its own from lane 32 (j & 1) + (j >> 1)
+    const int mysum = __builtin_amdgcn_ds_bpermute(((lane & 1) * 32 + (lane >> 1)) * 4, w[0]);
+    const bool mine = (pend >> lane) & 1ull;
+    const float d8 = metric_finish(sk_scale * (float)mysum, a.metric);
+    // (1 - dot, -dot and the subtraction below round once each: 3 x 2^-24 of magnitudes below 1 + |d8| + eps)
+    const float slack = sk_eps + 4e-7f * (1.0f + fabsf(d8) + sk_eps);
+    out = __ballot(mine && d8 - slack > tail_d);
+    return pend & ~out;
   }
 };
 
@@ -1923,7 +2056,7 @@ struct NoVisited {
 // (4 KB) next to the search set's; past 750 ids it spills to its HBM bitset like the big one does.
 constexpr uint32_t kHashCapResult = 1024;
 
-// does the distance policy have the two-precision stage (PlainDist<..., SK = true>)?
+// does the distance policy have the two-precision stage (PlainDist<..., SK = true>, Int8Dist)?
 template <class D, class = void>
 struct sketch_policy { static constexpr bool value = false; };
 template <class D>

@@ -175,13 +175,14 @@ class IndexVamana:
               "sketch": 13, "sketch_filtered": 14}  # SDB_TUNE_* (semadb_amd.h)
 
     def sketch_stats(self):
-        """(neighbours discarded on their float16 distance, contradicted by the exact distance [audit], copy in use)"""
+        """(neighbours discarded on their float16 / int8 distance, contradicted by the exact distance [audit], copy in use)"""
         out = (C.c_uint64 * 3)()
         check(lib().sdb_index_sketch_stats(self._h, out))
         return int(out[0]), int(out[1]), bool(out[2])
 
     def set_tuning(self, key, value):
-        """test / measurement knobs of this index (sdb_index_set_tuning); none changes a result"""
+        """test / measurement knobs of this index (sdb_index_set_tuning); none changes a result.  "sketch": 0 off, 1 / 2 the
+        float16 first stage (2: audited), 3 / 4 the int8 first stage where the table has one (4: audited; 3 is the default)"""
         check(lib().sdb_index_set_tuning(self._h, self.TUNING[key], int(value)))
 
     BUILD_STATS = ("search_n_dist", "search_n_edges", "prune_pairs", "backedge_pairs", "backedge_cached",

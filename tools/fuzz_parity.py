@@ -568,6 +568,132 @@ def two_precision_sums(results):
     return sums
 
 
+# ---------------------------------------------------------------------------------------------- the int8 first stage
+INT8_WIDTHS = (32, 64, 96, 128, 160, 256, 320, 352, 384)
+
+
+def int8_trial(rng, device=True):
+    """One random cosine / dot table of a width that has the int8 first stage (SDB_TUNE_SKETCH = 3, the default; 4 with
+    audit), through the one-wave walk: the replays equal the oracle's walks; on the device the answers equal the replays
+    under knobs 4, 3, 1 and 0, no discard is contradicted, and -- while the float64 model (tests/int8_stage_model.py) keeps
+    the int8 copy, with the scale and the maxima carried as the index carries them -- the number discarded lies between
+    the model's two counts.  A table the model refuses the copy (rows far below the table's scale) walks with the float16
+    copy: answers and audit only.  Returns {"desc": .., "batches": [(lower, discarded, upper) or None]}."""
+    from tests import int8_stage_model as M8
+    from tests import two_precision_model as M
+    d = int(rng.choice(INT8_WIDTHS))
+    metric = str(rng.choice(["cosine", "dot"]))
+    kind = str(rng.choice(["unit", "latent", "grid", "dups"], p=[0.4, 0.4, 0.1, 0.1]))
+    R = int(rng.integers(8, 65))
+    L = int(rng.integers(max(R // 2, 5), 97))
+    n = int(rng.integers(300, min(1500, 300000 // d) + 1))
+    desc = dict(int8_trial=True, d=d, metric=metric, kind=kind, R=R, L=L, n=n)
+    CURRENT.clear()
+    CURRENT.update(desc)
+    if VERBOSE:
+        print("  int8:", desc, file=sys.stderr, flush=True)
+    sv = start_vector(np.random.default_rng(int(rng.integers(1 << 30))), d)
+    o = orc.Index(d, metric, R, L, 1.2, impl=M.impl_of(orc))
+    o.set_start(sv)
+    base = draw_rows(rng, n, d, kind)
+    ids = np.arange(2, n + 2, dtype=np.uint64)
+    assert o.insert_rounds(ids, base) == 0
+    out = {"desc": desc, "batches": []}
+    g = None
+    if device:
+        g = vamana.NewIndexVamana("i8", vamana.IndexVectorVamanaParameters(d, metric, L, R, 1.2), strict=False)
+        g.set_tuning("wide_walk", 1)
+    state = {"copy": None, "refused": False}
+
+    def batch(tag):
+        ex = o.export()
+        gr = M.Graph(*ex)
+        q = draw_rows(rng, TP_QUERIES, d, kind)
+        q[11] = M.hostile_queries(d, TP_HOSTILE[int(rng.integers(len(TP_HOSTILE)))], seed=int(rng.integers(1 << 20)))[0]
+        limit = int(rng.integers(1, 21))
+        sl = int(rng.integers(limit, 97))
+        CURRENT["stage"] = "%s: limit %d searchSize %d" % (tag, limit, sl)
+        c = state["copy"]
+        full = M8.Copy8(gr.vecs, scale=c.scale)
+        full.emax, full.ymax = c.emax, c.ymax
+        reps, t, _, _ = M8.run_model8(orc, gr, metric, q, limit, sl, full)
+        for i in range(TP_QUERIES):
+            o_ids, o_d, o_vis, o_tr = o.search(q[i], limit, sl)
+            r = reps[i]
+            assert np.array_equal(r.ids, o_ids) and _tp_same_bits(r.dists, o_d) and np.array_equal(r.visit, o_vis), (tag, "replay != oracle", i)
+            assert (r.n_hop, r.n_dist, r.n_edges) == (o_tr.n_hop, o_tr.n_dist, o_tr.n_edges), (tag, "replay != oracle", i)
+        assert t.lower <= t.upper <= t.discardable <= t.full, (tag, "model", repr(t))
+        rec = None if state["refused"] else [t.lower, None, t.upper]
+        out["batches"].append(rec)
+        if not device:
+            return
+        for mode in (4, 3, 1, 0):
+            if state["refused"] and mode in (4, 3):
+                continue  # (setting the knob would ask for the int8 copy again: the table is left with what it holds)
+            g.set_tuning("sketch", mode)
+            ans, discarded, contradicted, in_use = _tp_walk(g, q, limit, sl, None)
+            what = (tag, "sketch=%d" % mode, "lower %d / discarded on the device %d / upper %d, contradicted %d" % (t.lower, discarded, t.upper, contradicted))
+            assert in_use == (mode != 0) and contradicted == 0, what
+            _tp_equals_replay(ans, reps, what)
+            if mode in (4, 3):
+                assert t.lower <= discarded <= t.upper, what
+                rec[1] = discarded
+        if not state["refused"]:
+            g.set_tuning("sketch", 3)  # the default again
+
+    try:
+        if device:
+            g.load(*o.export())
+            check_graph(g, o)
+        state["all_rows"] = o.export()[1]  # every row of the slab, the start node's included
+        state["copy"] = M8.Copy8(state["all_rows"])
+        state["refused"] = state["copy"].refused()
+        batch("after build")
+        live = [int(v) for v in ids]
+        for step in range(int(rng.integers(1, 3))):
+            n_ins = int(rng.integers(1, 60))
+            new_vecs = draw_rows(rng, n_ins, d, kind)
+            scale = float(rng.choice([1.0, 1.0, 0.5, 1.5, 1e-3]))
+            new_vecs = (new_vecs * np.float32(scale)).astype(np.float32)
+            n_del = int(rng.integers(0, max(1, len(live) // 8)))
+            dels = [int(v) for v in rng.choice(live, size=n_del, replace=False)] if n_del else []
+            first_new = max(live) + 1
+            new_ids = list(range(first_new, first_new + n_ins))
+            wr = int(rng.choice([1, 0, 64]))
+            CURRENT["stage"] = "step %d: %d inserts x %g (round_size %d), %d deletes" % (step, n_ins, scale, wr, len(dels))
+            if device:
+                ch = [vamana.IndexVectorChange(i, new_vecs[k]) for k, i in enumerate(new_ids)]
+                ch += [vamana.IndexVectorChange(i, None) for i in dels]
+                g.InsertUpdateDelete(ch, round_size=wr)
+            if wr == 1:
+                for k, i in enumerate(new_ids):
+                    assert o.insert(i, new_vecs[k]) == 0
+            else:
+                assert o.insert_rounds(np.array(new_ids, dtype=np.uint64), new_vecs, round_size=wr) == 0
+            if dels:
+                assert o.delete(np.array(dels, dtype=np.uint64)) == 0
+            live = sorted((set(live) - set(dels)) | set(new_ids))
+            c = state["copy"]
+            if not state["refused"]:
+                if M8.absmax(new_vecs) <= c.amax:  # inside the range: the scale stays, the maxima are carried
+                    new = M8.Copy8(new_vecs, scale=c.scale)
+                    c.emax, c.ymax, c.rel = max(c.emax, new.emax), max(c.ymax, new.ymax), max(c.rel, new.rel)
+                else:  # every row converted again (deleted rows keep their slots until compact: still counted)
+                    amax = max(float(c.amax), float(M8.absmax(new_vecs)))
+                    c = M8.Copy8(np.vstack([state["all_rows"], new_vecs]), scale=M8.scale_of(amax))
+                    c.amax = np.float32(amax)
+                    state["copy"] = c
+                state["refused"] = state["copy"].refused()
+            state["all_rows"] = np.vstack([state["all_rows"], new_vecs])
+            if device:
+                check_graph(g, o)
+            batch("after write step %d" % step)
+    finally:
+        if g is not None:
+            g.close()
+    return out
+
+
 def merge_trial(rng):
     """the shard fan-out's merge (cluster/actions.go:357-376) on random ragged per-shard results with ties"""
     from semadb_amd import cluster

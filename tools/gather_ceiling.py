@@ -1,6 +1,7 @@
 """Practical ceiling for the search kernel's access shape: random slab rows, half-wave per row, no dependencies
 (tools/probe/gather_probe.hip).  Prints achieved GB/s for the C2 (d = 384) and C4 (d = 768) row sizes at several
-occupancies, next to a plain streaming read of the same slab."""
+occupancies, next to a plain streaming read of the same slab.  --stage: the two-precision hop's first-stage rows at
+d = 384 instead -- 64 rows in flight per wave, float16 rows of 768 bytes against int8 rows of 384 bytes."""
 import ctypes
 import json
 import os
@@ -17,6 +18,27 @@ lib.gather_probe.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, 
 dev = "cuda:0"
 out = {}
 sink = torch.zeros(1 << 20, device=dev)
+if len(sys.argv) > 1 and sys.argv[1] == "--stage":
+    lib.gather_probe_stage.restype = ctypes.c_float
+    lib.gather_probe_stage.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    n, stream = 1000000, torch.cuda.current_stream().cuda_stream
+    for eb, name in ((2, "float16 rows, 768 B"), (1, "int8 rows, 384 B")):
+        rows = torch.randint(0, 127, (n, 384 * eb), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        res = {}
+        for waves in (1024, 2048):
+            iters = (5000 * 1024) // (waves * 64)  # ~5M rows per launch: what one batch of 1024 queries asks for
+            lib.gather_probe_stage(rows.data_ptr(), n, 3, eb, waves, iters, sink.data_ptr(), stream)
+            ms = min(lib.gather_probe_stage(rows.data_ptr(), n, 3, eb, waves, iters, sink.data_ptr(), stream) for _ in range(5))
+            assert ms > 0, ms
+            nrows = waves * iters * 64
+            res["waves=%d" % waves] = {"ms": round(ms, 4), "rows": nrows, "GB/s": round(nrows * 384 * eb / ms / 1e6, 1),
+                                       "Grows/s": round(nrows / ms / 1e6, 3)}
+        out["d=384 n=%d %s" % (n, name)] = res
+        del rows
+    print(json.dumps(out, indent=1))
+    sys.exit(0)
 shapes = ((384, 1000000), (768, 1000000), (128, 2000000))
 if len(sys.argv) > 1 and sys.argv[1] == "--big":  # the C5-rank and C4 slabs: how far the ceiling itself falls with size
     shapes = ((384, 4000000), (384, 12500000), (768, 10000000))

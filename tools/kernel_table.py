@@ -30,10 +30,12 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # them; the filtered forms of the walk carry six more list pointers and get SGPR_FILTERED; everything else SGPR_ANY
 # (the run-time-length fallbacks of the quantizer kernels sit at 112 .. 135).
 # The C2 walk is the two-precision hop's (PlainDist<NG, L2, true, 4, true>, the default since SDB_TUNE_SKETCH is on),
-# with the float32 walk (PlainDist<NG, L2, true, 0, false>, the opt-out) beside it; both metrics, both timed.
+# with the float32 walk (PlainDist<NG, L2, true, 0, false>, the opt-out) beside it; both metrics, both timed.  Cosine / dot
+# rows of up to 384 floats walk with the int8 first stage by default (Int8Dist<NG>, SDB_TUNE_SKETCH = 3): timed too.
 SGPR_TIMED, SGPR_FILTERED, SGPR_ANY = 64, 128, 160
 TIMED = re.compile(
     r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, false|4, true)>, 2, (false|true), 8192u>"
+    r"|k_greedy_search<sdb::Int8Dist<(1|2|3)>, 2, false, 8192u>"
     r"|k_greedy_search<sdb::BitDist<(false|true)>, "  # the bit-code walks (tools/bench_bq.py times the hamming one)
     r"|k_greedy_search_wide<(3|6), false, (8|16), (false|true)>"
     r"|k_greedy_search_pq2<|k_greedy_search_pqw<15, 33, 4294967295u, 4, 15, true>"
@@ -129,6 +131,7 @@ def markdown(rows):
 # the kernels DESIGN.md's register table shows: what the BASELINE configurations launch in their timed regions
 DESIGN = re.compile(
     r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, false|4, true)>, 2, false, 8192u>"
+    r"|k_greedy_search<sdb::Int8Dist<3>, 2, false, 8192u>"
     r"|k_greedy_search_wide<3, false, (8|16), false>|k_greedy_search_pq2<4294967295u>"
     r"|k_greedy_search_pqw<15, 33, 4294967295u, 4, 15, true>|k_pq_lut_t<true, (3, 96|0, 4)>|k_pq_encode_t<true, 3, true>"
     r"|k_pq_encode_pair<true, 4>|k_km_assign_t<(3, 96|0, 4)>|k_backedges<3, false>|k_prune_new<3, false>"

@@ -81,6 +81,66 @@ extern "C" float gather_probe(const float *slab, uint32_t n_rows, uint32_t ld, u
   return ms;
 }
 
+// ---- first-stage rows of the two-precision hop: 64 rows in flight per wave (32 pairs, a half-wave per row) -----------
+// EB = 2: the float16 copy's shape -- NG loads of 8 bytes per lane and row, 256 bytes apart (rows of NG * 256 bytes).
+// EB = 1: the int8 copy's shape -- a lane's 4 NG bytes of a row are contiguous, ONE load of NG dwords (rows of NG * 128 bytes).
+template <int NG, int EB>
+__global__ __launch_bounds__(64) void k_gather_probe_stage(const char *__restrict__ rows, uint32_t n_rows, uint32_t iters,
+                                                           float *__restrict__ out) {
+  const int lane = threadIdx.x, L = lane & 31, half = lane >> 5;
+  constexpr int W = EB == 2 ? 2 * NG : NG;  // dwords per lane and row
+  constexpr uint32_t kRowBytes = NG * 128 * EB;
+  struct __attribute__((packed, aligned(4))) Words { uint32_t w[NG]; };
+  uint32_t state = (blockIdx.x + 1) * 2654435761u;
+  uint32_t acc = 0;
+  for (uint32_t it = 0; it < iters; it++) {
+    uint32_t y[32][W];
+#pragma unroll
+    for (int u = 0; u < 32; u++) {
+      state = state * 1664525u + 1013904223u;
+      uint32_t x = state + half * 0x9E3779B9u;
+      x ^= x >> 16, x *= 0x85EBCA6Bu, x ^= x >> 13, x *= 0xC2B2AE35u, x ^= x >> 16;
+      const uint32_t r = (uint32_t)(((uint64_t)x * n_rows) >> 32);
+      const char *row = rows + (size_t)r * kRowBytes;
+      if constexpr (EB == 2) {
+#pragma unroll
+        for (int g = 0; g < NG; g++) {
+          const uint2 v = *reinterpret_cast<const uint2 *>(row + g * 256 + L * 8);
+          y[u][2 * g] = v.x, y[u][2 * g + 1] = v.y;
+        }
+      } else {
+        const Words v = *reinterpret_cast<const Words *>(row + L * 4 * NG);
+#pragma unroll
+        for (int g = 0; g < NG; g++) y[u][g] = v.w[g];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 32; u++)
+#pragma unroll
+      for (int g = 0; g < W; g++) acc += y[u][g];
+  }
+  if (acc == 0x12345679u) out[blockIdx.x * 64 + lane] = 1.0f;  // (keeps the loads)
+}
+
+// kernel time in ms, < 0 on error; rows read = waves * iters * 64, of ng * 128 * elem_bytes bytes each
+extern "C" float gather_probe_stage(const void *rows, uint32_t n_rows, uint32_t ng, uint32_t elem_bytes, uint32_t waves,
+                                    uint32_t iters, float *out, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ng != 3 || (elem_bytes != 1 && elem_bytes != 2)) return -2.0f;
+  hipEvent_t e0, e1;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0f;
+  (void)hipEventRecord(e0, s);
+  if (elem_bytes == 2) hipLaunchKernelGGL((k_gather_probe_stage<3, 2>), dim3(waves), dim3(64), 0, s, (const char *)rows, n_rows, iters, out);
+  else hipLaunchKernelGGL((k_gather_probe_stage<3, 1>), dim3(waves), dim3(64), 0, s, (const char *)rows, n_rows, iters, out);
+  const int rc = (int)hipGetLastError();
+  (void)hipEventRecord(e1, s);
+  if (rc != 0 || hipEventSynchronize(e1) != hipSuccess) return -3.0f;
+  float ms = 0.0f;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
+  return ms;
+}
+
 // ---- dependent-fetch probe: what ONE dependent HBM round trip costs a lone lane ------------------------------------
 // A graph walk's hop begins with a fetch whose address the previous hop produced.  Lane 0 of each wave chases through
 // `buf`: the next address is a hash of the word just loaded, so no two loads overlap.  One wave = the unloaded figure;

@@ -1,5 +1,6 @@
-"""Two-precision hop (SDB_TUNE_SKETCH) against the default walk on the headline shape: same ids, distance bits, visit
-counters for every timed batch; the audit's count of contradicted decisions; kernel time both ways."""
+"""Two-precision hop (SDB_TUNE_SKETCH: 1 the float16 first stage, 3 the int8 one) against the float32 walk on the
+headline shape: same ids, distance bits, visit counters for every timed batch; the audits' counts of contradicted
+decisions; kernel time of each, then 0 / 1 / 3 again in alternation (ROUNDS rounds, per-round figures kept)."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -39,7 +40,7 @@ def run(tag):
 
 
 ref, ref_tr = run("default")
-for mode, tag in ((2, "sketch_audit"), (1, "sketch")):
+for mode, tag in ((2, "sketch_audit"), (1, "sketch"), (4, "int8_audit"), (3, "int8")):
     ix.set_tuning("sketch", mode)
     got, got_tr = run(tag)
     same = all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) for a, b in zip(ref, got))
@@ -49,4 +50,11 @@ for mode, tag in ((2, "sketch_audit"), (1, "sketch")):
 ix.set_tuning("sketch", 0)
 again, _ = run("default_again")
 out["default_again"]["identical_results"] = bool(all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(ref, again)))
+rounds = {"float32": [], "sketch": [], "int8": []}
+for _ in range(int(os.environ.get("ROUNDS", 3))):
+    for mode, tag in ((0, "float32"), (1, "sketch"), (3, "int8")):
+        ix.set_tuning("sketch", mode)
+        run("_round")
+        rounds[tag].append(out.pop("_round")["kernel_ms_min"])
+out["alternating_kernel_ms_min"] = rounds
 print(json.dumps(out))

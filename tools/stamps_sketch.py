@@ -1,5 +1,5 @@
 """Per-hop cycle sums of the SDB_STAMPS diagnostic build (SEMADB_AMD_LIB) for the default walk and the two-precision
-hop on the headline shape: adjacency round trip, visited-set test, distances (both stages), AddWithLimit."""
+hop (1: float16 first stage, 3: int8 first stage) on the headline shape: adjacency round trip, visited-set test, distances (both stages), AddWithLimit."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -11,7 +11,7 @@ q = bench.gen_rows(4 * nq, d, 20250621, "latent:24", "cuda:0").view(4, nq, d)
 ix = vamana.NewIndexVamana("st", vamana.IndexVectorVamanaParameters(d, "cosine", 75, 64, 1.2), capacity=n + 1)
 ix.set_start(bench.start_vector(d))
 ix.insert_batch(None, base)
-for mode in (0, 1):
+for mode in (0, 1, 3):
     ix.set_tuning("sketch", mode)
     for b in range(3):
         ids, dd, c, tr = ix.search_batch(q[b], 10, 75, trace=True, visit_cap=8)
