@@ -190,17 +190,17 @@ struct sdb_index {
   // and within-margin neighbours (4 d each) stay below the float16 stage's 2.86 d, i.e. while kept + within-margin stays
   // below 0.41 of the evaluated; DESIGN 4 records the replay that turns that share into this ratio.
   static constexpr float kSketch8MaxRatio = 0.16f;
-  bool sketch8_supported() const;  // sketch_supported(), cosine / dot, ng 1 .. 3
+  bool sketch8_supported() const;  // sketch_supported() and search_kernel.h stage_int8(): cosine / dot, rows of up to 384 floats
   bool sketch8_wanted() const { return tune_sketch >= 3 && !tune_sketch_filtered && !sketch8_refused && sketch8_supported(); }  // (SDB_TUNE_SKETCH_FILTERED: the filtered hop reads the float16 copy)
   size_t sketch_row_bytes(bool int8) const { return int8 ? (size_t)lay.ld : (size_t)lay.ld * 2; }
-  uint16_t *d_sketch = nullptr;
+  void *d_sketch = nullptr;  // rows of ld halves, or (sketch8) of ld bytes
   float *d_sketch_norm = nullptr;  // [sketch_cap] ||y16||^2 per row (the euclidean form of the first stage)
   uint32_t sketch_cap = 0;   // rows d_sketch has room for
   std::atomic<uint64_t> sketch_gen{0};  // view_gen the copy was built for (0: none); written under the exclusive view_mu
   float sk_emax = 0.0f, sk_ymax = 0.0f;
   unsigned long long *d_sk_counters = nullptr;  // [0] neighbours discarded on their float16 distance, [1] contradicted (audit)
   std::mutex sketch_mu;  // held by build_sketch on the commit path (view_mu released) and by the knob: lock order sketch_mu, view_mu
-  // plain rows of whole 32-float blocks in one of the walk's register layouts (ng 1, 2, 3, 4, 6), any metric, no quantizer
+  // plain rows of whole 32-float blocks in one of the walk's register layouts (search_kernel.h stage_shape()), any metric, no quantizer
   bool sketch_supported() const;
   bool sketch_current() const { return d_sketch && sketch_gen == view_gen; }  // describes the current view's rows
   static bool sketch_room(size_t bytes);  // the device keeps max(4 GB, total / 16) free after `bytes` more (a cache's rule, build.hip pairc)

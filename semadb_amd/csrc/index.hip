@@ -560,9 +560,8 @@ static int launch_wide(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
 // to the bitset kernel: the LDS sets spill to the query's bitsets by themselves (HashVisited::spill clears the bitset
 // first), so such a call needs no bitset cleared ahead either (sketch_walk() is asked by the launcher and by the clear).
 bool sketch_walk(const SearchArgs &a, uint32_t nq) {
-  if (!a.sketch || a.pq_codes || a.bq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
-  if (!(a.ng == 1 || a.ng == 2 || a.ng == 3 || a.ng == 4 || a.ng == 6)) return false;
-  if (a.sk8 && (a.ng > 3 || a.metric == SDB_METRIC_EUCLIDEAN || a.filt_off)) return false;  // (the int8 copy: Int8Dist's tables and calls only)
+  if (a.stage == Stage::kNone || a.pq_codes || a.bq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
+  if (!stage_shape((int)a.ng)) return false;
   if (wide_walk(a, nq)) return false;
   return search_uses_hash(a, nq) || (a.filt_off && !a.prefer_bitset);
 }
@@ -572,18 +571,18 @@ static int launch_plain(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
   if constexpr (NG >= 1 && NG <= 8)
     if (wide_walk(a, nq)) return launch_wide<NG, L2>(a, nq, stream);
   const bool hash = search_uses_hash(a, nq);
-  if constexpr (NG == 1 || NG == 2 || NG == 3 || NG == 4 || NG == 6)
+  if constexpr (stage_shape(NG))
     if (sketch_walk(a, nq)) {
-      // (few float32 rows survive the first stage: four pairs of them in flight per round leave the registers to the float16 rows)
-      if constexpr (!L2 && NG <= 3)
-        if (a.sk8) {  // the int8 first stage (SDB_TUNE_SKETCH = 3, 4): plain calls of cosine / dot tables
+      // (few float32 rows survive the first stage: four pairs of them in flight per round leave the registers to the copy's rows)
+      if constexpr (stage_int8(NG, L2, false))
+        if (a.stage == Stage::kInt8) {  // the int8 first stage (SDB_TUNE_SKETCH = 3, 4): plain calls of cosine / dot tables
           using Sk8Dist = Int8Dist<NG>;
           hipLaunchKernelGGL((k_greedy_search<Sk8Dist, 2, false, kHashCap>), dim3(nq), dim3(64),
                              HashVisited<kHashCap>::kWords * sizeof(uint32_t) + Sk8Dist::kLdsBytes, stream, a);
           SDB_HIP(hipGetLastError());
           return SDB_OK;
         }
-      using SkDist = PlainDist<NG, L2, true, 4, true>;
+      using SkDist = PlainDist<NG, L2, true, 4, Stage::kHalf>;
       const size_t lds = HashVisited<kHashCap>::kWords * sizeof(uint32_t) + SkDist::kLdsBytes;
       if (a.filt_off)  // all three filter forms; the threshold is search_kernel.h list_tail_bound
         hipLaunchKernelGGL((k_greedy_search<SkDist, 2, true, kHashCap>), dim3(nq), dim3(64),
@@ -762,7 +761,7 @@ int sdb_index::reserve(uint32_t rows) {
   // insert_batch into a grown table may find no headroom left for its pair cache (build.hip pairc) and build without
   // it -- slower, same graph -- rather than have every search fall back to float32 rows.
   const bool sk_keep = sketch_current();
-  uint16_t *nsk = nullptr;
+  void *nsk = nullptr;
   float *nskn = nullptr;
   if (sk_keep && sketch_cap < ncap) {
     // (the int8 copy: rows of ld bytes and no per-row floats)
@@ -945,7 +944,7 @@ __global__ __launch_bounds__(256) void k_sketch_rows(const float *__restrict__ s
   }
 }
 
-// ---- the int8 copy (SDB_TUNE_SKETCH = 3, 4; search_kernel.h Int8Dist) ----
+// ---- the int8 copy (SDB_TUNE_SKETCH = 3, 4; search_kernel.h Int8Rows) ----
 // the largest |element| of `count` floats into *out (a NaN's pattern is above every number's)
 __global__ __launch_bounds__(256) void k_sketch8_absmax(const float *__restrict__ v, size_t count, uint32_t *__restrict__ out) {
   uint32_t m = 0;
@@ -994,12 +993,12 @@ __global__ __launch_bounds__(256) void k_sketch8_rows(const float *__restrict__ 
 }  // namespace sdb
 
 bool sdb_index::sketch8_supported() const {
-  return sketch_supported() && P.metric != SDB_METRIC_EUCLIDEAN && lay.ng <= 3;
+  return sketch_supported() && stage_int8((int)lay.ng, P.metric == SDB_METRIC_EUCLIDEAN, false);
 }
 
 bool sdb_index::sketch_supported() const {
   if (lay.tail != 0 || pq || bq) return false;
-  return lay.ng == 1 || lay.ng == 2 || lay.ng == 3 || lay.ng == 4 || lay.ng == 6;
+  return stage_shape((int)lay.ng);
 }
 
 bool sdb_index::sketch_room(size_t bytes) {
@@ -1069,7 +1068,7 @@ int sdb_index::build_sketch_kind(hipStream_t stream, uint32_t from, bool locked,
       return 1;
     }
   }
-  uint16_t *const sk = d_sketch;
+  void *const sk = d_sketch;
   float *const sk_norm = d_sketch_norm;
   uint32_t *stats = reinterpret_cast<uint32_t *>(d_sk_counters + 2);  // four words: the two maxima; int8: + the new rows' largest |element|, the largest relative row error
   uint32_t h[4] = {0, 0, 0, 0};
@@ -1105,10 +1104,10 @@ int sdb_index::build_sketch_kind(hipStream_t stream, uint32_t from, bool locked,
   if (ok && rows > from) {
     if (int8)
       hipLaunchKernelGGL(sdb::k_sketch8_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
-                         reinterpret_cast<uint8_t *>(sk) + (size_t)from * ld, rows - from, ld, ng, scale, stats);
+                         static_cast<uint8_t *>(sk) + (size_t)from * ld, rows - from, ld, ng, scale, stats);
     else
       hipLaunchKernelGGL(sdb::k_sketch_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
-                         sk + (size_t)from * ld, sk_norm + from, rows - from, ld, stats);
+                         static_cast<uint16_t *>(sk) + (size_t)from * ld, sk_norm + from, rows - from, ld, stats);
     ok = hipGetLastError() == hipSuccess;
   }
   ok = ok && hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, stream) == hipSuccess;
@@ -2069,17 +2068,20 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
   a.wide_hash = ix->tune_wide_hash ? 1u : 0u, a.hash16_probes = ix->tune_hash16_probes;
   a.pq_narrow = ix->tune_pq_narrow;
   a.wide_mode = ix->tune_wide_walk;
-  // two-precision hop: only with the float16 copy of exactly this view's rows, outside a write transaction.  Every
-  // field is read once, under the shared lock the writer's changes to them exclude.
+  // two-precision hop: only with the copy of exactly this view's rows, outside a write transaction.  Every field is read
+  // once, under the shared lock the writer's changes to them exclude.  This call's stage is decided here, once: the int8
+  // copy serves the calls stage_int8() names (a filtered call reads float32 rows then), the float16 copy every plain
+  // call and -- opt-in, SDB_TUNE_SKETCH_FILTERED -- the filtered ones.
   {
     const uint32_t knob = ix->tune_sketch;
-    const uint16_t *sk = ix->d_sketch;
-    if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx &&
-        (!filtered || ix->tune_sketch_filtered))  // (filtered calls: opt-in, SDB_TUNE_SKETCH_FILTERED)
+    const void *sk = ix->d_sketch;
+    if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx) {
+      if (ix->sketch8) a.stage = stage_int8((int)l.ng, ix->P.metric == SDB_METRIC_EUCLIDEAN, filtered) ? Stage::kInt8 : Stage::kNone;
+      else a.stage = (!filtered || ix->tune_sketch_filtered) ? Stage::kHalf : Stage::kNone;
+    }
+    if (a.stage != Stage::kNone)
       a.sketch = sk, a.sketch_norm = ix->d_sketch_norm, a.sk_emax = ix->sk_emax, a.sk_ymax = ix->sk_ymax,
-      a.sk_audit = (knob == 2 || knob == 4) ? 1u : 0u, a.sk_counters = ix->d_sk_counters,
-      a.sk8 = ix->sketch8 ? 1u : 0u, a.sk8_scale = ix->sk8_scale;
-    if (a.sk8 && filtered) a.sketch = nullptr, a.sk8 = 0;  // (the int8 stage is the plain calls'; a filtered call reads float32 rows)
+      a.sk_audit = (knob == 2 || knob == 4) ? 1u : 0u, a.sk_counters = ix->d_sk_counters, a.sk8_scale = ix->sk8_scale;
   }
 
   const uint32_t vcap = trace ? trace->visit_cap : 0;

@@ -24,6 +24,16 @@
 
 namespace sdb {
 
+// The two-precision hop's first stage: which copy of the rows a walk reads first (SearchArgs::sketch), if any.
+enum class Stage : uint32_t { kNone = 0, kHalf = 1, kInt8 = 2 };
+// Which tables and calls get which stage -- stated here once, for the launcher, the index and the kernels alike.
+// A stage at all: the group counts whose float16 rounds fit the walk's registers.
+constexpr bool stage_shape(int ng) { return ng == 1 || ng == 2 || ng == 3 || ng == 4 || ng == 6; }
+// Rows asked for ahead: rows of up to 384 floats, where all 64 edges' copy rows fit the register file.
+constexpr bool stage_ahead(int ng) { return stage_shape(ng) && ng <= 3; }
+// The int8 stage: those tables, cosine / dot, plain calls (a filtered call reads the float16 copy or none).
+constexpr bool stage_int8(int ng, bool euclidean, bool filtered) { return stage_ahead(ng) && !euclidean && !filtered; }
+
 struct SearchArgs {
   const float *slab;
   const uint32_t *adj;
@@ -88,11 +98,11 @@ struct SearchArgs {
   // `ld` halves.  A neighbour whose float16 distance lies above the candidate array's last distance by more than the
   // bound on |float16 distance - the reference's float32 distance| is discarded by AddWithLimit whatever its exact
   // distance is (distset.go:184; the distance is never looked at again), so only the others are read in float32.
-  const uint16_t *sketch;
+  const void *sketch;                // Stage::kHalf: rows of `ld` halves; Stage::kInt8: rows of `ld` bytes
   const float *sketch_norm;          // [rows] ||y16||^2 of every row (euclidean tables: d16 = ||q16||^2 + ||y16||^2 - 2 q16.y16)
-  float sk_emax, sk_ymax;            // max over the rows of ||y - y16|| and of ||y16|| (k_sketch_rows), rounded up
-  uint32_t sk8;                      // != 0: `sketch` is the INT8 copy (Int8Dist): rows of `ld` bytes, sk_emax / sk_ymax its maxima
-  float sk8_scale;                   // the table's scale s of that copy: y8 = clamp(rint(y / s), -127, 127)
+  float sk_emax, sk_ymax;            // max over the rows of ||y - y16|| and of ||y16|| (k_sketch_rows), rounded up; the int8 copy's likewise
+  Stage stage;                       // this call's first stage, decided once where the arguments are filled (index.hip); kNone: `sketch` is NULL
+  float sk8_scale;                   // the int8 copy's scale s: y8 = clamp(rint(y / s), -127, 127)
   uint32_t sk_audit;                 // != 0: evaluate everything exactly as well and count decisions the exact distance contradicts
   unsigned long long *sk_counters;   // [0] += neighbours discarded on their float16 distance, [1] += contradicted ones (audit)
   // binary-quantized store (binary.go:187-200): per-slot codes [n][W] of 64-bit words, the threshold [dim] the walk
@@ -230,72 +240,30 @@ __device__ __forceinline__ void chunk_dist_lds(const float *__restrict__ slab, u
   }
 }
 
-// ---- distance policies: what vecStore.DistanceFromFloat(query) binds (plain.go:76-85 / product.go:238-277)
-
-// Full-precision store.  NG >= 0: compile-time group count, query in registers.  NG == -1: run-time
-// ng, query tile in LDS.
 typedef _Float16 sk_h2 __attribute__((ext_vector_type(2)));
 // float -> float16 as the sketch stores it: round to nearest, magnitudes below the smallest NORMAL half become 0 (no
 // denormal half is ever an operand of v_dot2_f32_f16, whatever the mode register says about them); what this loses is
 // part of the measured error ||v - v16||, not an assumption
 __device__ __forceinline__ _Float16 sk_half(float v) { return fabsf(v) < 6.103515625e-5f ? (_Float16)0.0f : (_Float16)v; }
 
-template <int NG, bool L2, bool DEEP = false, int UPAIRS = 0, bool SK = false>  // UPAIRS != 0: that many pairs of rows per chunk; SK: two-precision hop
-struct PlainDist {
-  static constexpr bool kSketch = SK;
-  static constexpr bool kHasStamps = true;
-  static constexpr bool kPointDistances = true;  // dist(query, row) is distFn between two stored vectors
-  // search_body: nothing is worked ahead on between the hops.  (Round 5 tried the walker's naming of the next hop's row
-  // here too -- its adjacency row asked for under AddWithLimit, a round trip less per hop in the batch's tail: 0.983
-  // against 0.975 ms per batch, the naming's ~300 instructions per hop cost a lone wave more than the hidden latency.
-  // The cheap half -- no naming, only the adjacency row of the array's first unvisited entry asked for before
-  // AddWithLimit and taken from the register when the walk does go there -- made no difference at all: 0.955 / 0.958 /
-  // 0.957 against 0.957 / 0.954 / 0.973 ms in alternating runs; the batch walk is bound by bytes, not by a wave's round trips.)
-#ifndef SDB_SKETCH_SPECULATE
-#define SDB_SKETCH_SPECULATE 0  // measurement builds (tools/sketch_ab.py): 1 measured 0.716 against 0.722 ms (min of 10) -- within the noise, off
-#endif
-  // ... with the two-precision hop the walk IS bound by its round trips; naming the next hop's adjacency row and asking
-  // for it before AddWithLimit runs (search_body's kSpeculate path without the small-call kernel's marker wave) was
-  // measured there too and moved the kernel by 1 %: the naming costs about what the hidden round trip saves
-  static constexpr bool kSpeculate = SK && SDB_SKETCH_SPECULATE;
-  static constexpr bool marked = false;  // (no marker wave: nothing is tested ahead)
-  __device__ __forceinline__ void take_marks(int, uint64_t &, uint32_t &) {}
-  static constexpr int NGR = NG > 0 ? NG : 1;
-  static constexpr int U = UPAIRS ? UPAIRS : (NG >= 0 ? ChunkPairs<NG, DEEP>::value : 4);
-  // dynamic LDS of the policy: NG == -1 the query tile; NG >= 0 the hop scratch -- pending slots by rank
-  // [kHopSlots], raw distances by rank [kHopSlots], a U-word dump
-  // (two-precision hop: pairs of float16 rows in flight per round -- all of a hop's new neighbours in ONE round where
-  // the registers allow it, 2 NG registers per row: a round is a dependent memory round trip of the hop)
-#ifndef SDB_SKETCH_ROWS
-#define SDB_SKETCH_ROWS 32  // measurement builds: tools/sketch_ab.py
-#endif
-  static constexpr int kSkBudget = L2 ? 72 : 96;  // (the euclidean exact stage holds differences as well)
-  static constexpr int US = !SK ? U : (SDB_SKETCH_ROWS < kSkBudget / NGR ? SDB_SKETCH_ROWS : kSkBudget / NGR);
-  static constexpr int UX = U > US ? U : US;
-  static constexpr uint32_t kHopSlots = 64 + UX;  // ranks 0..63 and the overrun of the last half-wave run
-  static constexpr size_t kLdsBytes = NG >= 0 ? (2 * kHopSlots + UX) * sizeof(uint32_t) : 0;
-  float4 xq[NGR];
-  float xt;
-  float *qs;
-  uint32_t *hs;
-  sk_h2 qh[SK ? NGR : 1][2];  // the query in float16, in xq's element order
-  float sk_eps;               // bound on |float16 distance - the reference's float32 distance| for this query, any row
-  float sk_qq, sk_delta;      // euclidean: ||q16||^2, and ||q - q16|| + max ||y - y16|| (rounded up)
-  float sk_yy;                // euclidean, rows asked for ahead: ||y16||^2 of this lane's edge
-  // Rows of up to 384 floats: the float16 rows of ALL 64 edges of an adjacency row fit the register file (2 NG registers
-  // per pair of rows), so they are asked for as soon as the edge ids are there -- BEFORE the visited-set test, whose
-  // LDS round trips (~2 100 cycles) then run under the rows' flight instead of in front of it.  Rows of edges that turn
-  // out to be visited already were read for nothing (a quarter more float16 bytes; the walk is not bound by bytes).
-#ifndef SDB_SKETCH_AHEAD
-#define SDB_SKETCH_AHEAD 1  // measurement builds: 0 = rows asked for after the test, compacted (tools/sketch_ab.py)
-#endif
-  static constexpr bool kSketchAhead = SK && SDB_SKETCH_AHEAD && NG >= 1 && NG <= 3;
-  uint2 sky[kSketchAhead ? 32 : 1][kSketchAhead ? NGR : 1];  // pair u: edge 2u (lanes 0..31) and edge 2u + 1 (lanes 32..63)
-  bool sk_go = false;        // search_body: this hop's rows are asked for ahead (the array is full, the copy is there)
-  bool sk_loaded = false;
-#ifdef SDB_STAMPS
-  unsigned long long st[3] = {0, 0, 0};  // issue, wait, compute
-#endif
+// ---- the two-precision hop's first stage (SearchArgs::sketch, SDB_TUNE_SKETCH): one implementation (FirstStage) over
+// two formats of the copy.  A format says how the query is converted and its error measured, how one copy row is
+// loaded and summed per lane, and how a complete sum becomes the dot product the verdict looks at.
+
+// The float16 format: rows of `ld` halves in the slab's element order; lane L's 4 elements of group g at byte
+// 256 g + 8 L of the row (NG loads per row, 256 bytes apart).
+template <int NG, bool L2>
+struct HalfRows {
+  typedef float sum_t;
+  struct row_t { uint2 g[NG]; };
+  static constexpr int kLaneBytes = 8, kElemBytes = 2;
+  static constexpr bool kCompacts = true;  // rows that were not asked for ahead are read by rank through LDS (range)
+  // pairs of rows in flight per round of that path -- all of a hop's new neighbours in ONE round where the registers allow
+  // it, 2 NG registers per row: a round is a dependent memory round trip of the hop
+  static constexpr int kBudget = L2 ? 72 : 96;  // (the euclidean exact stage holds differences as well)
+  static constexpr int kRound = 32 < kBudget / NG ? 32 : kBudget / NG;
+  sk_h2 qh[NG][2];      // the query in float16, in xq's element order
+  float qq, delta, yy;  // euclidean: ||q16||^2; ||q - q16|| + max ||y - y16|| (rounded up); rows ahead: ||y16||^2 of this lane's edge
 
   // The bound.  With q16, y16 the float16 copies (exact in float32): q.y - q16.y16 = (q - q16).y16 + q.(y - y16), so
   // |q.y - q16.y16| <= ||q - q16|| Ymax16 + ||q|| Emax (Cauchy-Schwarz; Emax, Ymax16 measured over all rows by
@@ -303,13 +271,14 @@ struct PlainDist {
   // rounding: the reference's 32 chains of NG x 4 / 32 ... fused multiply-adds and its 6-level tree, at most 4 NG + 6
   // roundings of relative size 2^-24 on sums bounded by ||q|| ||y||; the sketch's 2 NG v_dot2_f32_f16 (products of
   // halves are exact in float32, three additions each) and the same tree: 6 NG + 6.  For NG <= 8 that is below
-  // 110 x 2^-24 = 6.6e-6; 2e-5 ||q|| (Ymax16 + Emax) is charged.  Norms are inflated by 1e-4 for their own rounding; the
-  // final 1 - dot / -dot and the subtraction of the bound are covered per comparison (sketch_keep).  A query or a table
-  // with a non-finite or float16-overflowing element makes the bound infinite or NaN: nothing is discarded then.
-  __device__ __forceinline__ void init_sketch(const SearchArgs &a, int lane) {
+  // 110 x 2^-24 = 6.6e-6; 2e-5 ||q|| (Ymax16 + Emax) is charged (stage_eps).  Norms are inflated by 1e-4 for their own
+  // rounding; the final 1 - dot / -dot and the subtraction of the bound are covered per comparison (FirstStage::out).  A
+  // query or a table with a non-finite or float16-overflowing element makes the bound infinite or NaN: nothing is
+  // discarded then.
+  __device__ __forceinline__ void query(const float4 (&xq)[NG], int lane, const SearchArgs &c, float &qerr, float &qn) {
     float e2 = 0.0f, n2 = 0.0f;
 #pragma unroll
-    for (int g = 0; g < NGR; g++) {
+    for (int g = 0; g < NG; g++) {
       const float v[4] = {xq[g].x, xq[g].y, xq[g].z, xq[g].w};
       _Float16 h[4];
 #pragma unroll
@@ -322,20 +291,32 @@ struct PlainDist {
     }
     // (both halves of the wave hold the same query: the sum over one half's 32 lanes)
     e2 = rlf(asm_reduce(e2, 0.0f, lane), 0), n2 = rlf(asm_reduce(n2, 0.0f, lane), 0);
-    const float qerr = __builtin_sqrtf(e2) * 1.0001f, qn = __builtin_sqrtf(n2) * 1.0001f;
-    const SearchArgs &c = cold_args(a);  // (what only the hop reads: through the opaque view, not parked in SGPRs)
-    sk_eps = (qerr * c.sk_ymax + qn * c.sk_emax + 2e-5f * qn * (c.sk_ymax + c.sk_emax)) * 1.0001f;
+    qerr = __builtin_sqrtf(e2) * 1.0001f, qn = __builtin_sqrtf(n2) * 1.0001f;
     if constexpr (L2) {
       float hh = 0.0f;
 #pragma unroll
-      for (int g = 0; g < NGR; g++) {
+      for (int g = 0; g < NG; g++) {
         const float h0 = (float)qh[g][0][0], h1 = (float)qh[g][0][1], h2 = (float)qh[g][1][0], h3 = (float)qh[g][1][1];
         hh = __builtin_fmaf(h0, h0, hh), hh = __builtin_fmaf(h1, h1, hh), hh = __builtin_fmaf(h2, h2, hh), hh = __builtin_fmaf(h3, h3, hh);
       }
-      sk_qq = rlf(asm_reduce(hh, 0.0f, lane), 0);
-      sk_delta = (qerr + c.sk_emax) * 1.0001f;
+      qq = rlf(asm_reduce(hh, 0.0f, lane), 0);
+      delta = (qerr + c.sk_emax) * 1.0001f;
     }
   }
+  static __device__ __forceinline__ void load(row_t &y, const char *r) {
+#pragma unroll
+    for (int g = 0; g < NG; g++) y.g[g] = *reinterpret_cast<const uint2 *>(r + g * 256);
+  }
+  __device__ __forceinline__ float partial(const row_t &y) const {
+    float acc = 0.0f;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+      acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, y.g[g].x), qh[g][0], acc, false);
+      acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, y.g[g].y), qh[g][1], acc, false);
+    }
+    return acc;
+  }
+  __device__ __forceinline__ float dot(float sum16) const { return sum16; }
 
   // Squared euclidean distance.  With D16 = ||q16 - y16||^2 (exact) and delta >= ||q - q16|| + ||y - y16||:
   // | sqrt(D) - sqrt(D16) | <= delta, so D >= D16 - 2 delta sqrt(D16) (when sqrt(D16) < delta the right side is
@@ -343,121 +324,309 @@ struct PlainDist {
   // sums: its error is below 1e-5 (||q16||^2 + ||y16||^2 + 2 |q16.y16|) (the same roundings as the dot form, 2^-24 each for
   // the two norms, three more for the combination -- well under 100 x 2^-24 = 6e-6).  The reference's own sum of rounded
   // squares of rounded differences is within (NG x 4 + 10) x 2^-24 < 1e-5 of D, relatively (all terms are >= 0).
-  __device__ __forceinline__ bool sketch_out(const SearchArgs &a, float sum16, float yy, float tail_d) const {
-    if constexpr (L2) {
-      const float d16 = (sk_qq + yy) - 2.0f * sum16;
-      const float err = 1e-5f * (sk_qq + yy + 2.0f * fabsf(sum16)) + 1e-30f;
-      const float up = d16 + err;  // D16 <= up
-      const float root = __builtin_sqrtf(up > 0.0f ? up : 0.0f) * 1.00001f;  // >= sqrt(D16)
-      const float lower = ((d16 - err) - 2.0f * sk_delta * root) * (1.0f - 2e-5f);  // <= the reference's distance, rounding of this line included below
-      return lower - 1e-6f * (fabsf(d16) + err + sk_delta * root) > tail_d;  // (the roundings of the two lines above; a NaN anywhere: false)
-    } else {
-      const float d16 = metric_finish(sum16, a.metric);
-      // (1 - dot, -dot and the subtraction below round once each: 3 x 2^-24 of magnitudes below 1 + |d16| + eps)
-      const float slack = sk_eps + 4e-7f * (1.0f + fabsf(d16) + sk_eps);
-      return d16 - slack > tail_d;
-    }
+  __device__ __forceinline__ bool out_l2(float sum16, float yy_row, float tail_d) const {
+    const float d16 = (qq + yy_row) - 2.0f * sum16;
+    const float err = 1e-5f * (qq + yy_row + 2.0f * fabsf(sum16)) + 1e-30f;
+    const float up = d16 + err;  // D16 <= up
+    const float root = __builtin_sqrtf(up > 0.0f ? up : 0.0f) * 1.00001f;  // >= sqrt(D16)
+    const float lower = ((d16 - err) - 2.0f * delta * root) * (1.0f - 2e-5f);  // <= the reference's distance, rounding of this line included below
+    return lower - 1e-6f * (fabsf(d16) + err + delta * root) > tail_d;  // (the roundings of the two lines above; a NaN anywhere: false)
   }
 
-  // float16 dot products of the pending rows by rank, two rows per wave instruction like rows_range
-  __device__ __forceinline__ void sketch_range(const SearchArgs &a, const uint32_t *s_slot, float *s_res, int cnt, int lane) {
+  // float16 dot products of the pending rows by rank, two rows per wave instruction like PlainDist::rows_range; `dump`
+  // takes the writes of the lanes that hold no result
+  __device__ __forceinline__ void range(const SearchArgs &a, const uint32_t *s_slot, float *s_res, float *dump, int cnt, int lane) const {
     const int L = lane & 31, half = lane >> 5;
-    const char *baseL = reinterpret_cast<const char *>(cold_args(a).sketch) + L * 8;
-    const uint32_t row_bytes = a.ld * 2u;
-    for (int c0 = 0; c0 < cnt; c0 += 2 * US) {
-      const int m = cnt - c0 < 2 * US ? cnt - c0 : 2 * US;
+    const char *baseL = static_cast<const char *>(cold_args(a).sketch) + L * kLaneBytes;
+    const uint32_t row_bytes = a.ld * kElemBytes;
+    for (int c0 = 0; c0 < cnt; c0 += 2 * kRound) {
+      const int m = cnt - c0 < 2 * kRound ? cnt - c0 : 2 * kRound;
       const int h0 = (m + 1) >> 1;
       const int base = c0 + (half ? h0 : 0);
-      uint32_t sl[US];
+      uint32_t sl[kRound];
 #pragma unroll
-      for (int u = 0; u < US; u++) sl[u] = s_slot[base + u];
-      uint2 y[US][NGR];
+      for (int u = 0; u < kRound; u++) sl[u] = s_slot[base + u];
+      row_t y[kRound];
 #pragma unroll
-      for (int u = 0; u < US; u++)
-        if (u < h0) {
-          const char *r = baseL + (uint64_t)sl[u] * row_bytes;
+      for (int u = 0; u < kRound; u++)
+        if (u < h0) load(y[u], baseL + (uint64_t)sl[u] * row_bytes);
+      float *wp = (L == 0) ? s_res + base : dump;
 #pragma unroll
-          for (int g = 0; g < NG; g++) y[u][g] = *reinterpret_cast<const uint2 *>(r + g * 256);
-        }
-      float *wp = (L == 0) ? s_res + base : s_res + kHopSlots;  // the other lanes write to a dump
+      for (int u = 0; u < kRound; u++)
+        if (u < h0) wp[u] = asm_reduce(partial(y[u]), 0.0f, lane);
+    }
+  }
+};
+
+// The int8 format (SDB_TUNE_SKETCH = 3; cosine / dot, rows of 128 .. 384 floats): the index keeps
+// y8 = clamp(rint(y / s), -127, 127) of every row, one scale s per table (index.hip k_sketch8_rows), in place of the
+// float16 copy -- half the bytes of the stage that reads a row for every edge of every hop.  A copy row is ld bytes; lane
+// L's 4 NG bytes of it are contiguous (bytes [4 NG L, 4 NG (L + 1)): group g's elements 4 L .. 4 L + 3 at + 4 g), so a
+// lane asks for a row with ONE load of NG dwords.
+//
+// The query becomes two int8 terms once per wave: with s_q = max |q_i| / 127, a = clamp(rint(q / s_q)) and
+// b = clamp(rint((q - s_q a) 128 / s_q)) (the residual of a, |b| <= 64), q^ = (s_q / 128) (128 a + b).  Per row and lane
+// W = (sum a y8 << 7) + sum b y8 from 2 NG v_dot4_i32_i8 -- an exact integer, |W| <= 16 320 x 127 x 384 < 2^31 -- and the
+// 32 sums of a hop go through the transposing butterfly as INTEGER adds: nothing is rounded before the one conversion
+// d8 = metric_finish((s s_q / 128) float(W)), and q^ . y^ = (s s_q / 128) W exactly with y^ = s y8.
+//
+// The bound, as for the float16 format: q.y - q^.y^ = (q - q^).y^ + q.(y - y^), so |q.y - q^.y^| <= ||q - q^|| Y8max +
+// ||q|| E8max (Cauchy-Schwarz; E8max = max ||y - s y8|| and Y8max = max ||s y8|| measured in double over all rows and
+// rounded up by k_sketch8_rows; ||q - q^|| and ||q|| measured here).  ||q - q^|| is measured against the float32 value
+// of q^_i, one rounding (2^-24 |q^_i|) away from the exact product: 2e-7 ||q|| is added.  The reference's float32 chain
+// and tree round 4 NG + 6 times (2^-24 each, on sums bounded by ||q|| ||y||); d8's scale product, conversion and
+// multiplication three times: below 21 x 2^-24 = 1.3e-6 for NG <= 3, and 2e-5 ||q|| (Y8max + E8max) is charged, the
+// term the float16 format charges (stage_eps).  Norms are inflated by 1e-4 for their own rounding; the final 1 - dot /
+// -dot and the subtraction of the bound are covered per comparison (FirstStage::out: 4e-7 of the magnitudes, which also
+// covers a scale product that underflows).  A query or a table with a non-finite element makes the bound infinite or
+// NaN: nothing is discarded then.  A survivor goes straight to the float32 stage (PlainDist::hop): reference order,
+// same bits.
+template <int NG>
+struct Int8Rows {
+  static_assert(stage_int8(NG, false, false), "a hop's 64 int8 rows are held in 32 NG registers");
+  typedef int sum_t;
+  struct row_t { uint32_t w[NG]; };
+  static constexpr int kLaneBytes = 4 * NG, kElemBytes = 1;
+  static constexpr bool kCompacts = false;  // (never needed: the rows are asked for ahead whenever the array is full)
+  uint32_t qa[NG], qb[NG];  // four int8 each, in xq's element order
+  float scale;              // s s_q / 128
+
+  __device__ __forceinline__ void query(const float4 (&xq)[NG], int lane, const SearchArgs &c, float &qerr, float &qn) {
+    float mx = 0.0f;
 #pragma unroll
-      for (int u = 0; u < US; u++)
-        if (u < h0) {
-          float acc = 0.0f;
+    for (int g = 0; g < NG; g++)
+      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xq[g].x), fabsf(xq[g].y)), fmaxf(fabsf(xq[g].z), fabsf(xq[g].w))));
+    // (fmaxf drops a NaN: a query with one is caught by the measured error below, which becomes NaN)
 #pragma unroll
-          for (int g = 0; g < NG; g++) {
-            acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, y[u][g].x), qh[g][0], acc, false);
-            acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, y[u][g].y), qh[g][1], acc, false);
-          }
-          wp[u] = asm_reduce(acc, 0.0f, lane);
-        }
+    for (int o = 16; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float sq = mx / 127.0f, inv = sq > 0.0f ? 1.0f / sq : 0.0f, sq128 = sq * 0.0078125f;
+    float e2 = 0.0f, n2 = 0.0f;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+      const float v[4] = {xq[g].x, xq[g].y, xq[g].z, xq[g].w};
+      uint32_t pa = 0, pb = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float fa = fminf(fmaxf(__builtin_rintf(v[k] * inv), -127.0f), 127.0f);
+        const float fb = fminf(fmaxf(__builtin_rintf((v[k] - sq * fa) * inv * 128.0f), -127.0f), 127.0f);
+        const float dv = v[k] - sq128 * (fa * 128.0f + fb);  // (128 a + b is exact in float32)
+        e2 = __builtin_fmaf(dv, dv, e2), n2 = __builtin_fmaf(v[k], v[k], n2);
+        pa |= ((uint32_t)(int)fa & 0xFFu) << (8 * k), pb |= ((uint32_t)(int)fb & 0xFFu) << (8 * k);
+      }
+      qa[g] = pa, qb[g] = pb;
+    }
+    // (both halves of the wave hold the same query: the sum over one half's 32 lanes)
+    e2 = rlf(asm_reduce(e2, 0.0f, lane), 0), n2 = rlf(asm_reduce(n2, 0.0f, lane), 0);
+    qn = __builtin_sqrtf(n2) * 1.0001f, qerr = __builtin_sqrtf(e2) * 1.0001f + 2e-7f * qn;
+    scale = c.sk8_scale * sq128;
+  }
+  static __device__ __forceinline__ void load(row_t &y, const char *r) {
+    struct __attribute__((packed, aligned(4))) RowWords { uint32_t w[NG]; };
+    const RowWords p = *reinterpret_cast<const RowWords *>(r);
+#pragma unroll
+    for (int g = 0; g < NG; g++) y.w[g] = p.w[g];
+  }
+  __device__ __forceinline__ int partial(const row_t &y) const {
+    int sa = 0, sb = 0;
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+      sa = __builtin_amdgcn_sdot4((int)y.w[g], (int)qa[g], sa, false);
+      sb = __builtin_amdgcn_sdot4((int)y.w[g], (int)qb[g], sb, false);
+    }
+    return sa * 128 + sb;
+  }
+  __device__ __forceinline__ float dot(int w) const { return scale * (float)w; }
+};
+
+// One stage of the transposing butterfly: at stride S a lane keeps the rows whose bit S equals its own and hands the
+// others to lane ^ S.
+template <int S, class T>
+__device__ __forceinline__ void butterfly_stage(T (&w)[32], int lane) {
+  const bool up = (lane & S) != 0;
+#pragma unroll
+  for (int i = 0; i < S; i++) {
+    const T keep = up ? w[i + S] : w[i], send = up ? w[i] : w[i + S];
+    w[i] = keep + __builtin_bit_cast(T, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, send), (S << 10) | 0x1F));
+  }
+}
+// 32 sums per half-wave (pair u: edge 2u in lanes 0..31, edge 2u + 1 in lanes 32..63), each spread over the 32 lanes.
+// Instead of 32 reductions that each end in one lane (and a trip through LDS to get edge j's sum to lane j), one
+// transposing butterfly: 16 + 8 + 4 + 2 + 1 exchanges instead of 32 x 5, and lane L of a half ends with the complete sum
+// of pair L.  One ds_bpermute then puts edge j's sum into lane j.  (Any order of additions is within the float16 bound,
+// and integer sums are exact; no LDS memory is touched.)
+template <class T>
+__device__ __forceinline__ T edge_sums(T (&w)[32], int lane) {
+  butterfly_stage<16>(w, lane), butterfly_stage<8>(w, lane), butterfly_stage<4>(w, lane), butterfly_stage<2>(w, lane);
+  butterfly_stage<1>(w, lane);
+  // lane 32 h + L holds edge 2 L + h: lane j takes its own from lane 32 (j & 1) + (j >> 1)
+  return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(((lane & 1) * 32 + (lane >> 1)) * 4, __builtin_bit_cast(int, w[0])));
+}
+
+// bound on |first-stage dot product - the reference's float32 one| for a query, any row (derived above each format)
+__device__ __forceinline__ float stage_eps(float qerr, float qn, float ymax, float emax) {
+  return (qerr * ymax + qn * emax + 2e-5f * qn * (ymax + emax)) * 1.0001f;
+}
+
+// A float32-only walk carries no stage state.  (Held as a plain one-byte member, not [[no_unique_address]] and not an empty
+// base: either moves Int8Dist's members and costs its NG = 3 kernel a VGPR, 229 for 228; a stage as a base in front of xq
+// measured 235.)
+struct NoStage {};
+
+template <class Fmt, bool L2, bool AHEAD>
+struct FirstStage {
+  typedef typename Fmt::row_t row_t;
+  typedef typename Fmt::sum_t sum_t;
+  Fmt fmt;
+  float eps;  // stage_eps of this query
+  // Rows of up to 384 floats (stage_ahead): the copy rows of ALL 64 edges of an adjacency row fit the register file, so
+  // they are asked for as soon as the edge ids are there -- BEFORE the visited-set test, whose LDS round trips (~2 100
+  // cycles) then run under the rows' flight instead of in front of it.  Rows of edges that turn out to be visited already
+  // were read for nothing (a quarter more copy bytes; the walk is not bound by bytes).  (Asking after the test,
+  // compacted, was the measured alternative and lost; HISTORY.md keeps the figures.)
+  bool loaded = false;
+  row_t y[AHEAD ? 32 : 1];  // pair u: edge 2u (lanes 0..31) and edge 2u + 1 (lanes 32..63); (kept last: with the rows in
+                            // front of the flag the int8 walk at NG = 3 takes 233 registers for 228)
+
+  template <int NG>
+  __device__ __forceinline__ void init(const SearchArgs &a, const float4 (&xq)[NG], int lane) {
+    const SearchArgs &c = cold_args(a);  // (what only the hop reads: through the opaque view, not parked in SGPRs)
+    float qerr, qn;
+    fmt.query(xq, lane, c, qerr, qn);
+    eps = stage_eps(qerr, qn, c.sk_ymax, c.sk_emax);
+  }
+
+  // A hop asks for its copy rows ahead with the array full.  The walk is launched only with the copy (index.hip
+  // launch_plain), so the pointer need not be tested -- and untested, the compiler sees that keep()'s compacting path is
+  // never taken with the rows asked for ahead: 87 -> 14 spilled SGPRs at NG = 3 (cosine / dot).  The euclidean walk keeps
+  // the test (through the opaque view): untested, this compiler spills 4 VGPRs there; tested, none.
+  __device__ __forceinline__ void begin(const SearchArgs &a, uint32_t nb, bool valid, bool full) {
+    if constexpr (AHEAD) {
+      loaded = false;
+      if constexpr (L2) full = full && cold_args(a).sketch != nullptr;
+      if (!full) return;
+      const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      const int L = lane & 31;
+      const bool hi = lane >= 32;
+      // (the copy's addresses through the opaque view at each use: one scalar load, where arguments that live through
+      // the walk would hold SGPR pairs spilled into VGPR lanes -- tools/kernel_table.py)
+      const char *baseL = static_cast<const char *>(cold_args(a).sketch) + L * Fmt::kLaneBytes;
+      const uint32_t row_bytes = a.ld * Fmt::kElemBytes;
+      const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
+#pragma unroll
+      for (int u = 0; u < 32; u++) {
+        const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
+        Fmt::load(y[u], baseL + (uint64_t)(hi ? s1 : s0) * row_bytes);
+      }
+      if constexpr (L2) fmt.yy = cold_args(a).sketch_norm[safe];
+      loaded = true;
     }
   }
 
-  // the pending neighbours that AddWithLimit may keep: `out` gets the ones whose float16 distance is above `tail_d` by
-  // more than the bound (every comparison with a NaN is false: such a neighbour is kept for the exact evaluation)
-  __device__ __forceinline__ uint64_t sketch_keep(const SearchArgs &a, uint32_t nb, uint64_t pend, int lane, float tail_d,
-                                                  uint64_t &out) {
-    if constexpr (kSketchAhead) {
-      if (sk_loaded) {  // the rows are in registers, by edge position
-        // 32 sums per half-wave (pair u: edge 2u in lanes 0..31, edge 2u + 1 in lanes 32..63), each spread over the 32
-        // lanes.  Instead of 32 reductions that each end in one lane (and a trip through LDS to get edge j's sum to lane
-        // j), one transposing butterfly: at stride s a lane keeps the rows whose bit s equals its own and hands the
-        // others to lane ^ s -- 16 + 8 + 4 + 2 + 1 exchanges instead of 32 x 5, and lane L of a half ends with the
-        // complete sum of pair L.  One ds_bpermute then puts edge j's sum into lane j.  (Any order of additions is within
-        // the bound; no LDS memory is touched.)
-        float w[32];
-#pragma unroll
-        for (int u = 0; u < 32; u++) {
-          float acc = 0.0f;
-#pragma unroll
-          for (int g = 0; g < NG; g++) {
-            acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, sky[u][g].x), qh[g][0], acc, false);
-            acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(sk_h2, sky[u][g].y), qh[g][1], acc, false);
-          }
-          w[u] = acc;
-        }
-#define SDB_SK_STAGE(S)                                                                                         \
-  {                                                                                                             \
-    const bool up = (lane & (S)) != 0;                                                                          \
-    _Pragma("unroll") for (int i = 0; i < (S); i++) {                                                           \
-      const float keep = up ? w[i + (S)] : w[i], send = up ? w[i] : w[i + (S)];                                 \
-      w[i] = keep + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(send), ((S) << 10) | 0x1F));      \
-    }                                                                                                           \
+  // is the neighbour's reference distance provably above `tail_d`?  (every comparison with a NaN is false)
+  __device__ __forceinline__ bool out(const SearchArgs &a, sum_t sum, float yy, float tail_d) const {
+    if constexpr (L2) {
+      return fmt.out_l2(sum, yy, tail_d);
+    } else {
+      const float d = metric_finish(fmt.dot(sum), a.metric);
+      // (1 - dot, -dot and the subtraction below round once each: 3 x 2^-24 of magnitudes below 1 + |d| + eps)
+      const float slack = eps + 4e-7f * (1.0f + fabsf(d) + eps);
+      return d - slack > tail_d;
+    }
   }
-        SDB_SK_STAGE(16)
-        SDB_SK_STAGE(8)
-        SDB_SK_STAGE(4)
-        SDB_SK_STAGE(2)
-        SDB_SK_STAGE(1)
-#undef SDB_SK_STAGE
-        // lane 32 h + L holds edge 2 L + h: lane j takes its own from lane 32 (j & 1) + (j >> 1)
-        const float mysum = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane & 1) * 32 + (lane >> 1)) * 4, __float_as_int(w[0])));
+
+  // the pending neighbours that AddWithLimit may keep: `out` gets the ones whose first-stage distance is above `tail_d`
+  // by more than the bound (a NaN: such a neighbour is kept for the exact evaluation).  hs: the policy's hop scratch,
+  // slots by rank [hop_slots], sums by rank [hop_slots], a dump.
+  __device__ __forceinline__ uint64_t keep(const SearchArgs &a, uint32_t *hs, uint32_t hop_slots, uint32_t nb, uint64_t pend,
+                                           int lane, float tail_d, uint64_t &outm) {
+    if constexpr (AHEAD) {
+      if (loaded) {  // the rows are in registers, by edge position
+        sum_t w[32];
+#pragma unroll
+        for (int u = 0; u < 32; u++) w[u] = fmt.partial(y[u]);
+        const sum_t mysum = edge_sums(w, lane);
         const bool mine = (pend >> lane) & 1ull;
-        out = __ballot(mine && sketch_out(a, mysum, L2 ? sk_yy : 0.0f, tail_d));
-        return pend & ~out;
+        float yy = 0.0f;
+        if constexpr (L2) yy = fmt.yy;
+        const bool above = out(a, mysum, yy, tail_d);  // (for every lane: no branch around the arithmetic)
+        outm = __ballot(mine && above);
+        return pend & ~outm;
       }
     }
-    const int cnt = __popcll(pend);
-    const bool mine = (pend >> lane) & 1ull;
-    float yy_me = 0.0f;
-    if constexpr (L2)
-      if (mine) yy_me = cold_args(a).sketch_norm[nb];  // (in flight while the rows are summed)
-    const uint32_t rank =
-        __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
-    uint32_t *s_slot = hs;
-    float *s_res = reinterpret_cast<float *>(hs + kHopSlots);
-    if (mine) {
-      s_slot[rank] = nb;
-      if ((int)rank == cnt - 1) s_slot[cnt] = nb;  // the spare entry
+    if constexpr (Fmt::kCompacts) {
+      const int cnt = __popcll(pend);
+      const bool mine = (pend >> lane) & 1ull;
+      float yy_me = 0.0f;
+      if constexpr (L2)
+        if (mine) yy_me = cold_args(a).sketch_norm[nb];  // (in flight while the rows are summed)
+      const uint32_t rank =
+          __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
+      uint32_t *s_slot = hs;
+      float *s_res = reinterpret_cast<float *>(hs + hop_slots);
+      if (mine) {
+        s_slot[rank] = nb;
+        if ((int)rank == cnt - 1) s_slot[cnt] = nb;  // the spare entry
+      }
+      wave_lds_sync();
+      fmt.range(a, s_slot, s_res, s_res + hop_slots, cnt, lane);
+      wave_lds_sync();
+      outm = __ballot(mine && out(a, s_res[rank], yy_me, tail_d));
+      wave_lds_sync();  // hop() compacts into the same scratch
+      return pend & ~outm;
+    } else {
+      outm = 0;
+      return pend;
     }
-    wave_lds_sync();
-    sketch_range(a, s_slot, s_res, cnt, lane);
-    wave_lds_sync();
-    out = __ballot(mine && sketch_out(a, s_res[rank], yy_me, tail_d));
-    wave_lds_sync();  // hop() compacts into the same scratch
-    return pend & ~out;
   }
+};
+
+// the stage a PlainDist holds itself: the float16 one (the int8 stage is held by its subclass, Int8Dist)
+template <int NG, bool L2, Stage ST>
+struct StageOf { typedef NoStage type; };
+template <int NG, bool L2>
+struct StageOf<NG, L2, Stage::kHalf> { typedef FirstStage<HalfRows<NG, L2>, L2, stage_ahead(NG)> type; };
+
+// ---- distance policies: what vecStore.DistanceFromFloat(query) binds (plain.go:76-85 / product.go:238-277)
+
+// Full-precision store.  NG >= 0: compile-time group count, query in registers.  NG == -1: run-time
+// ng, query tile in LDS.
+template <int NG, bool L2, bool DEEP = false, int UPAIRS = 0, Stage ST = Stage::kNone>  // UPAIRS != 0: that many pairs of rows per chunk; ST: two-precision hop
+struct PlainDist {
+  static constexpr Stage kStage = ST;
+  static constexpr bool kHasStamps = true;
+  static constexpr bool kPointDistances = true;  // dist(query, row) is distFn between two stored vectors
+  // search_body: nothing is worked ahead on between the hops.  (Round 5 tried the walker's naming of the next hop's row
+  // here too -- its adjacency row asked for under AddWithLimit, a round trip less per hop in the batch's tail: 0.983
+  // against 0.975 ms per batch, the naming's ~300 instructions per hop cost a lone wave more than the hidden latency.
+  // The cheap half -- no naming, only the adjacency row of the array's first unvisited entry asked for before
+  // AddWithLimit and taken from the register when the walk does go there -- made no difference at all: 0.955 / 0.958 /
+  // 0.957 against 0.957 / 0.954 / 0.973 ms in alternating runs; the batch walk is bound by bytes, not by a wave's round trips.)
+  // ... with the two-precision hop the walk IS bound by its round trips; naming the next hop's adjacency row and asking
+  // for it before AddWithLimit runs (search_body's kSpeculate path without the small-call kernel's marker wave) was
+  // measured there too: 0.716 against 0.722 ms (min of 10), within the noise -- the naming costs about what the hidden
+  // round trip saves.  Off.
+  static constexpr bool kSpeculate = false;
+  static constexpr bool marked = false;  // (no marker wave: nothing is tested ahead)
+  __device__ __forceinline__ void take_marks(int, uint64_t &, uint32_t &) {}
+  static constexpr int NGR = NG > 0 ? NG : 1;
+  static constexpr int U = UPAIRS ? UPAIRS : (NG >= 0 ? ChunkPairs<NG, DEEP>::value : 4);
+  // dynamic LDS of the policy: NG == -1 the query tile; NG >= 0 the hop scratch -- pending slots by rank
+  // [kHopSlots], raw distances by rank [kHopSlots], a UX-word dump (UX: the float16 stage's rounds may be longer than U)
+  static constexpr int stage_round() {
+    if constexpr (ST == Stage::kHalf) return HalfRows<NG, L2>::kRound;
+    return 0;
+  }
+  static constexpr int UX = U > stage_round() ? U : stage_round();
+  static constexpr uint32_t kHopSlots = 64 + UX;  // ranks 0..63 and the overrun of the last half-wave run
+  static constexpr size_t kLdsBytes = NG >= 0 ? (2 * kHopSlots + UX) * sizeof(uint32_t) : 0;
+  float4 xq[NGR];
+  float xt;
+  float *qs;
+  uint32_t *hs;
+  typename StageOf<NG, L2, ST>::type stage;
+#ifdef SDB_STAMPS
+  unsigned long long st[3] = {0, 0, 0};  // issue, wait, compute
+#endif
 
   __device__ __forceinline__ void init(const SearchArgs &a, uint32_t q, int lane, float *lds) {
     const int L = lane & 31;
@@ -472,7 +641,7 @@ struct PlainDist {
                             q_elem(qv, a.nblk, g, 2, L), q_elem(qv, a.nblk, g, 3, L));
       if (NG == 0) xq[0] = make_float4(0.f, 0.f, 0.f, 0.f);
       xt = (a.tail && (uint32_t)L < a.tail) ? qv[a.nblk * 32 + L] : 0.0f;
-      if constexpr (SK) init_sketch(a, lane);
+      if constexpr (ST == Stage::kHalf) stage.init(a, xq, lane);
     } else {
       for (uint32_t i = lane; i < a.ng * 128; i += 64) {
         uint32_t g = i / 128, r = i % 128;
@@ -503,37 +672,14 @@ struct PlainDist {
     return metric_finish(rlf(res[0], 0), a.metric);
   }
 
-  // Whether a hop asks for its float16 rows ahead: with the array full.  The walk is launched only with the copy
-  // (index.hip launch_plain), so the pointer need not be tested -- and untested, the compiler sees that sketch_keep's
-  // compacting path is never taken with the rows asked for ahead: 87 -> 14 spilled SGPRs at NG = 3 (cosine / dot).  The
-  // euclidean walk keeps the test (through the opaque view): untested, this compiler spills 4 VGPRs there; tested, none.
-  __device__ __forceinline__ bool sketch_go(const SearchArgs &a, bool full) const {
-    if constexpr (L2) return full && cold_args(a).sketch != nullptr;
-    return full;
+  // search_body's hooks of the two-precision hop: a hop's copy rows asked for, and the verdict.  These two are the
+  // float16 stage's; with ST == Stage::kInt8 this class holds no stage and is only Int8Dist's base, which brings its own
+  // (used directly, these two would not compile: NoStage has no begin / keep).
+  __device__ __forceinline__ void stage_begin(const SearchArgs &a, uint32_t nb, bool valid, bool full) { stage.begin(a, nb, valid, full); }
+  __device__ __forceinline__ uint64_t stage_keep(const SearchArgs &a, uint32_t nb, uint64_t pend, int lane, float tail_d, uint64_t &out) {
+    return stage.keep(a, hs, kHopSlots, nb, pend, lane, tail_d, out);
   }
-  __device__ __forceinline__ void prefetch(const SearchArgs &a, uint32_t nb, bool valid) {  // float32 rows are fetched in hop()
-    if constexpr (kSketchAhead) {
-      sk_loaded = false;
-      if (!sk_go) return;
-      const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      const int L = lane & 31;
-      const bool hi = lane >= 32;
-      // (the copy's addresses through the opaque view at each use: one scalar load, where arguments that live through
-      // the walk would hold SGPR pairs spilled into VGPR lanes -- tools/kernel_table.py)
-      const char *baseL = reinterpret_cast<const char *>(cold_args(a).sketch) + L * 8;
-      const uint32_t row_bytes = a.ld * 2u;
-      const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
-#pragma unroll
-      for (int u = 0; u < 32; u++) {
-        const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
-        const char *r = baseL + (uint64_t)(hi ? s1 : s0) * row_bytes;
-#pragma unroll
-        for (int g = 0; g < NG; g++) sky[u][g] = *reinterpret_cast<const uint2 *>(r + g * 256);
-      }
-      if constexpr (L2) sk_yy = cold_args(a).sketch_norm[safe];
-      sk_loaded = true;
-    }
-  }
+  __device__ __forceinline__ void prefetch(const SearchArgs &, uint32_t, bool) {}  // float32 rows are fetched in hop()
   __device__ __forceinline__ void speculation(bool, const uint32_t *) {}
   __device__ __forceinline__ void ahead(const SearchArgs &, const uint32_t *, int, bool) {}
   // hooks of the multi-wave quantized walk (PQWideDist); nothing to do for a one-wave policy
@@ -698,134 +844,20 @@ struct PlainDist {
   }
 };
 
-// The two-precision hop with an INT8 first stage (SDB_TUNE_SKETCH = 3; cosine / dot, rows of 128 .. 384 floats): the
-// index keeps y8 = clamp(rint(y / s), -127, 127) of every row, one scale s per table (index.hip k_sketch8_rows), in
-// place of the float16 copy -- half the bytes of the stage that reads a row for every edge of every hop.  A copy row is
-// ld bytes; lane L's 4 NG bytes of it are contiguous (bytes [4 NG L, 4 NG (L + 1)): group g's elements 4 L .. 4 L + 3
-// at + 4 g), so a lane asks for a row with ONE load of NG dwords where the float16 copy takes NG loads 256 bytes apart.
-//
-// The query becomes two int8 terms once per wave: with s_q = max |q_i| / 127, a = clamp(rint(q / s_q)) and
-// b = clamp(rint((q - s_q a) 128 / s_q)) (the residual of a, |b| <= 64), q^ = (s_q / 128) (128 a + b).  Per row and lane
-// W = (sum a y8 << 7) + sum b y8 from 2 NG v_dot4_i32_i8 -- an exact integer, |W| <= 16 320 x 127 x 384 < 2^31 -- and the
-// 32 sums of a hop go through the transposing butterfly as INTEGER adds: nothing is rounded before the one conversion
-// d8 = metric_finish((s s_q / 128) float(W)), and q^ . y^ = (s s_q / 128) W exactly with y^ = s y8.
-//
-// The bound, as for the float16 stage: q.y - q^.y^ = (q - q^).y^ + q.(y - y^), so |q.y - q^.y^| <= ||q - q^|| Y8max +
-// ||q|| E8max (Cauchy-Schwarz; E8max = max ||y - s y8|| and Y8max = max ||s y8|| measured in double over all rows and
-// rounded up by k_sketch8_rows; ||q - q^|| and ||q|| measured here).  ||q - q^|| is measured against the float32 value
-// of q^_i, one rounding (2^-24 |q^_i|) away from the exact product: 2e-7 ||q|| is added.  The reference's float32 chain
-// and tree round 4 NG + 6 times (2^-24 each, on sums bounded by ||q|| ||y||); d8's scale product, conversion and
-// multiplication three times: below 21 x 2^-24 = 1.3e-6 for NG <= 3, and 2e-5 ||q|| (Y8max + E8max) is charged, the
-// term the float16 stage charges.  Norms are inflated by 1e-4 for their own rounding; the final 1 - dot / -dot and the
-// subtraction of the bound are covered per comparison (sketch_out: 4e-7 of the magnitudes, which also covers a scale
-// product that underflows).  A query or a table with a non-finite element makes the bound infinite or NaN: nothing is
-// discarded then.  A survivor goes straight to the float32 stage (Base::hop): reference order, same bits.
+// The walk with the int8 first stage.  A subclass, not a third choice of PlainDist's `stage` member: held as that member
+// the same code takes 229 registers at NG = 3, here 228 (this compiler's allocation follows the object's layout).  It adds
+// the stage's state and the three calls that reach it; everything else, the float32 stage included, is the base's.
 template <int NG>
-struct Int8Dist : PlainDist<NG, false, true, 4, false> {
-  static_assert(NG >= 1 && NG <= 3, "a hop's 64 int8 rows are held in 32 NG registers");
-  using Base = PlainDist<NG, false, true, 4, false>;
-  static constexpr bool kSketch = true;
-  struct __attribute__((packed, aligned(4))) RowWords { uint32_t w[NG]; };
-  uint32_t qa[NG], qb[NG];  // four int8 each, in xq's element order
-  float sk_eps;             // bound on |d8 - the reference's float32 distance| for this query, any row
-  float sk_scale;           // s s_q / 128
-  uint32_t sky[32][NG];     // pair u: edge 2u (lanes 0..31) and edge 2u + 1 (lanes 32..63)
-  bool sk_go = false, sk_loaded = false;
-
+struct Int8Dist : PlainDist<NG, false, true, 4, Stage::kInt8> {
+  using Base = PlainDist<NG, false, true, 4, Stage::kInt8>;
+  FirstStage<Int8Rows<NG>, false, true> rows8;
   __device__ __forceinline__ void init(const SearchArgs &a, uint32_t q, int lane, float *lds) {
     Base::init(a, q, lane, lds);
-    float mx = 0.0f;
-#pragma unroll
-    for (int g = 0; g < NG; g++)
-      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(this->xq[g].x), fabsf(this->xq[g].y)), fmaxf(fabsf(this->xq[g].z), fabsf(this->xq[g].w))));
-    // (fmaxf drops a NaN: a query with one is caught by the measured error below, which becomes NaN)
-#pragma unroll
-    for (int o = 16; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    const float sq = mx / 127.0f, inv = sq > 0.0f ? 1.0f / sq : 0.0f, sq128 = sq * 0.0078125f;
-    float e2 = 0.0f, n2 = 0.0f;
-#pragma unroll
-    for (int g = 0; g < NG; g++) {
-      const float v[4] = {this->xq[g].x, this->xq[g].y, this->xq[g].z, this->xq[g].w};
-      uint32_t pa = 0, pb = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const float fa = fminf(fmaxf(__builtin_rintf(v[k] * inv), -127.0f), 127.0f);
-        const float fb = fminf(fmaxf(__builtin_rintf((v[k] - sq * fa) * inv * 128.0f), -127.0f), 127.0f);
-        const float dv = v[k] - sq128 * (fa * 128.0f + fb);  // (128 a + b is exact in float32)
-        e2 = __builtin_fmaf(dv, dv, e2), n2 = __builtin_fmaf(v[k], v[k], n2);
-        pa |= ((uint32_t)(int)fa & 0xFFu) << (8 * k), pb |= ((uint32_t)(int)fb & 0xFFu) << (8 * k);
-      }
-      qa[g] = pa, qb[g] = pb;
-    }
-    // (both halves of the wave hold the same query: the sum over one half's 32 lanes)
-    e2 = rlf(asm_reduce(e2, 0.0f, lane), 0), n2 = rlf(asm_reduce(n2, 0.0f, lane), 0);
-    const float qn = __builtin_sqrtf(n2) * 1.0001f, qerr = __builtin_sqrtf(e2) * 1.0001f + 2e-7f * qn;
-    const SearchArgs &c = cold_args(a);
-    sk_eps = (qerr * c.sk_ymax + qn * c.sk_emax + 2e-5f * qn * (c.sk_ymax + c.sk_emax)) * 1.0001f;
-    sk_scale = c.sk8_scale * sq128;
+    rows8.init(a, this->xq, lane);
   }
-
-  __device__ __forceinline__ bool sketch_go(const SearchArgs &, bool full) const { return full; }
-
-  __device__ __forceinline__ void prefetch(const SearchArgs &a, uint32_t nb, bool valid) {
-    sk_loaded = false;
-    if (!sk_go) return;
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const int L = lane & 31;
-    const bool hi = lane >= 32;
-    const char *baseL = reinterpret_cast<const char *>(cold_args(a).sketch) + L * (4 * NG);
-    const uint32_t row_bytes = a.ld;
-    const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
-#pragma unroll
-    for (int u = 0; u < 32; u++) {
-      const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
-      const RowWords r = *reinterpret_cast<const RowWords *>(baseL + (uint64_t)(hi ? s1 : s0) * row_bytes);
-#pragma unroll
-      for (int g = 0; g < NG; g++) sky[u][g] = r.w[g];
-    }
-    sk_loaded = true;
-  }
-
-  // the pending neighbours that AddWithLimit may keep: `out` gets the ones whose int8 distance is above `tail_d` by more
-  // than the bound (every comparison with a NaN is false: such a neighbour is kept for the exact evaluation)
-  __device__ __forceinline__ uint64_t sketch_keep(const SearchArgs &a, uint32_t, uint64_t pend, int lane, float tail_d,
-                                                  uint64_t &out) {
-    out = 0;
-    if (!sk_loaded) return pend;  // (never with the array full: the rows are asked for whenever it is)
-    // one transposing butterfly over the 32 pairs (PlainDist::sketch_keep), on integers
-    int w[32];
-#pragma unroll
-    for (int u = 0; u < 32; u++) {
-      int sa = 0, sb = 0;
-#pragma unroll
-      for (int g = 0; g < NG; g++) {
-        sa = __builtin_amdgcn_sdot4((int)sky[u][g], (int)qa[g], sa, false);
-        sb = __builtin_amdgcn_sdot4((int)sky[u][g], (int)qb[g], sb, false);
-      }
-      w[u] = sa * 128 + sb;
-    }
-#define SDB_SK8_STAGE(S)                                                                 \
-  {                                                                                      \
-    const bool up = (lane & (S)) != 0;                                                   \
-    _Pragma("unroll") for (int i = 0; i < (S); i++) {                                    \
-      const int keep = up ? w[i + (S)] : w[i], send = up ? w[i] : w[i + (S)];            \
-      w[i] = keep + __builtin_amdgcn_ds_swizzle(send, ((S) << 10) | 0x1F);               \
-    }                                                                                    \
-  }
-    SDB_SK8_STAGE(16)
-    SDB_SK8_STAGE(8)
-    SDB_SK8_STAGE(4)
-    SDB_SK8_STAGE(2)
-    SDB_SK8_STAGE(1)
-#undef SDB_SK8_STAGE
-    // lane 32 h + L holds edge 2 L + h: lane j takes its own from lane 32 (j & 1) + (j >> 1)
-    const int mysum = __builtin_amdgcn_ds_bpermute(((lane & 1) * 32 + (lane >> 1)) * 4, w[0]);
-    const bool mine = (pend >> lane) & 1ull;
-    const float d8 = metric_finish(sk_scale * (float)mysum, a.metric);
-    // (1 - dot, -dot and the subtraction below round once each: 3 x 2^-24 of magnitudes below 1 + |d8| + eps)
-    const float slack = sk_eps + 4e-7f * (1.0f + fabsf(d8) + sk_eps);
-    out = __ballot(mine && d8 - slack > tail_d);
-    return pend & ~out;
+  __device__ __forceinline__ void stage_begin(const SearchArgs &a, uint32_t nb, bool valid, bool full) { rows8.begin(a, nb, valid, full); }
+  __device__ __forceinline__ uint64_t stage_keep(const SearchArgs &a, uint32_t nb, uint64_t pend, int lane, float tail_d, uint64_t &out) {
+    return rows8.keep(a, this->hs, Base::kHopSlots, nb, pend, lane, tail_d, out);
   }
 };
 
@@ -1091,6 +1123,7 @@ struct PlainWideDist : PlainDist<NG, L2, true, WidePairs<NG, W, L2>::value> {
 // Fitted product quantizer: dist = sum_i lut[i*K + code_i], plain fp32 adds in index order
 // (product.go:271-275).  One lane per neighbour: all new neighbours of a hop in one pass.
 struct PQDist {
+  static constexpr Stage kStage = Stage::kNone;
   // (the same naming of the next hop's row, with its code rows fetched ahead: 0.419 against 0.359 ms per batch at
   // 4M x 768, M = 8 -- a one-wave hop is bound by its instruction count, not by the fetch; measured and removed)
   static constexpr bool kSpeculate = false;
@@ -1227,6 +1260,7 @@ struct PQDist {
 // once by init, the wave's ballots (binary.go:123-127) -- are read from LDS at a wave-uniform address.
 template <bool JACCARD>
 struct BitDist {
+  static constexpr Stage kStage = Stage::kNone;
   static constexpr bool kSpeculate = false;
   static constexpr bool kHasStamps = false;
   static constexpr bool kPointDistances = false;  // (the build's distance table is a full-precision store's)
@@ -1304,6 +1338,7 @@ __device__ __forceinline__ void add_with_limit_merge(uint32_t (&cid)[NREG], floa
 );
 template <int NL, int RT, int W = 4>
 struct PQWideDist {
+  static constexpr Stage kStage = Stage::kNone;
   // Fetching ahead (search_body, Dist::kSpeculate) was built for this walk too -- every wave fetched the likely next
   // row at the start of a hop and its neighbours' codes at the end of it, so that 70 % of the hops started with both in
   // registers -- and measured no gain at two queries per CU (M = 192, 1M x 768: 1.089 ms per batch against 1.04 without,
@@ -2056,12 +2091,6 @@ struct NoVisited {
 // (4 KB) next to the search set's; past 750 ids it spills to its HBM bitset like the big one does.
 constexpr uint32_t kHashCapResult = 1024;
 
-// does the distance policy have the two-precision stage (PlainDist<..., SK = true>, Int8Dist)?
-template <class D, class = void>
-struct sketch_policy { static constexpr bool value = false; };
-template <class D>
-struct sketch_policy<D, decltype((void)D::kSketch)> { static constexpr bool value = D::kSketch; };
-
 // greedySearch for one query by one wavefront.  RVis: the visited set of the filtered search's result set.
 template <class Dist, int NREG, bool FILT, class Visited, class RVis>
 __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t q, const int lane, Dist &dist,
@@ -2073,7 +2102,8 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
   int len = 0;
   const int cap = (int)a.search_size;
   uint32_t n_dist = 0, n_hop = 0, n_edges = 0;
-  uint32_t n_sk_out = 0;  // two-precision hop: neighbours discarded on their float16 distance
+  constexpr bool kStaged = Dist::kStage != Stage::kNone;  // the two-precision hop
+  uint32_t n_sk_out = 0;  // ... its neighbours discarded on their first-stage distance
   __shared__ uint32_t s_scatter[2 * NREG * 64];  // add_with_limit_merge scratch
 
   // filtered search (search.go:33-51): resultSet = DistSet(cap k) with its own visited set
@@ -2241,8 +2271,8 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
       if (!Dist::kSpeculate) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // charge the adjacency round trip to st_adj
 #endif
       SDB_STAMP(st_adj)
-      if constexpr (sketch_policy<Dist>::value) dist.sk_go = dist.sketch_go(a, len == cap);
-      dist.prefetch(a, nb, valid);
+      if constexpr (kStaged) dist.stage_begin(a, nb, valid, len == cap);
+      else dist.prefetch(a, nb, valid);
       // CheckAndVisit distset.go:174 -- marks before any distance test
       bool isnew;
       if (Dist::kSpeculate && have_marks && first_chunk) isnew = (mark_mask >> lane) & 1ull;
@@ -2251,7 +2281,7 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
       SDB_STAMP(st_atom)
       if (pend) {
         n_dist += (uint32_t)__popcll(pend);
-        if constexpr (sketch_policy<Dist>::value) {
+        if constexpr (kStaged) {
           // two-precision hop: with the array full, the neighbours whose float16 distance is provably above every last
           // distance the array can have at their turn are discarded here; AddWithLimit would discard them one by one
           // (distset.go:184) and nothing else ever reads their distance.  Plain walk: the array is sorted, its last
@@ -2261,7 +2291,7 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
           if (len == cap) {
             const float tail_d = FILT ? list_tail_bound(cd, cap, __popcll(pend), lane) : list_tail(cd, cap);
             uint64_t out = 0;
-            const uint64_t keep = dist.sketch_keep(a, nb, pend, lane, tail_d, out);
+            const uint64_t keep = dist.stage_keep(a, nb, pend, lane, tail_d, out);
             if (cold_args(a).sk_audit) {  // (rare path: counted at once, not carried in a register through the walk)
               const float dx = dist.hop(a, nb, pend, lane);
               const uint64_t bad = __ballot(((out >> lane) & 1ull) && !(dx > tail_d));
@@ -2313,15 +2343,14 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
           }
         }
         // AddWithLimit over the new neighbours, in edge order distset.go:184-198
-        if (!sketch_policy<Dist>::value || pend) {  // (the two-precision hop may have discarded every new neighbour)
+        if (!kStaged || pend) {  // (the two-precision hop may have discarded every new neighbour)
           if constexpr (FILT) add_with_limit_lanes(cid, cd, len, cap, nb, mydist, pend, lane);  // array may be unsorted
-#ifndef SDB_SKETCH_FEW
-#define SDB_SKETCH_FEW 2  // measurement builds (tools/sketch_ab.py): 7 measured 0.756 against 0.729 ms
-#endif
+          // (fewer than 2 candidates are replayed one by one; the two-precision hop hands over ~5 points per hop, and a
+          // threshold of 7 for it measured 0.756 against 0.729 ms)
 #ifdef SDB_STAMPS
-          else add_with_limit_merge<NREG, sketch_policy<Dist>::value ? SDB_SKETCH_FEW : 2>(cid, cd, len, cap, nb, mydist, pend, lane, s_scatter, st_m);
+          else add_with_limit_merge<NREG, 2>(cid, cd, len, cap, nb, mydist, pend, lane, s_scatter, st_m);
 #else
-          else add_with_limit_merge<NREG, sketch_policy<Dist>::value ? SDB_SKETCH_FEW : 2>(cid, cd, len, cap, nb, mydist, pend, lane, s_scatter);
+          else add_with_limit_merge<NREG, 2>(cid, cd, len, cap, nb, mydist, pend, lane, s_scatter);
 #endif
         }
         SDB_STAMP(st_ins)
@@ -2409,7 +2438,7 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
     if (e.tr_nedges) e.tr_nedges[q] = n_edges;
 #endif
     if (e.vis_count) e.vis_count[q] = n_hop;
-    if constexpr (sketch_policy<Dist>::value)
+    if constexpr (kStaged)
       if (e.sk_counters && n_sk_out) atomicAdd(e.sk_counters, (unsigned long long)n_sk_out);
     if (e.totals) {  // one of 64 copies of the counters (index.h kStatCopies)
       unsigned long long *t = e.totals + (q & 63u) * 16u;

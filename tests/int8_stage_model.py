@@ -8,7 +8,7 @@ kernel's arithmetic.  The walk, the replay and the tally are tests/two_precision
   q^ = (s_q / 128)(128 a + b), in the kernel's float32 steps;
 * the exact integer sum W = sum (128 a + b) y8 and d8 = metric(s (s_q / 128) W), exact in float64;
 * the bound: upper  d8 - (||q - q^|| Y8max + ||q|| E8max) > tail,
-             lower  the same with every inflation the kernel documents (search_kernel.h Int8Dist) charged generously.
+             lower  the same with every inflation the kernel documents (search_kernel.h Int8Rows) charged generously.
 
 The kernel's derivation implies  lower <= discarded on the device <= upper <= discardable.
 """
@@ -93,10 +93,10 @@ class Bounds8:
             d8 = (1.0 - dot8) if metric == "cosine" else -dot8
             eps = qerr * copy.ymax + qn * copy.emax
             self.upper = d8 - eps
-            # Int8Dist::init: qerr, ||q||, E8max, Y8max carry 1.0001 each and the sum another, float32 roundings on top;
+            # Int8Rows::query, stage_eps: qerr, ||q||, E8max, Y8max carry 1.0001 each and the sum another, float32 roundings on top;
             # charged 1.001.  qerr gets 2e-7 ||q|| for the rounding of q^'s float32 value; charged 3e-7 x 1.001 ||q|| Y8max.
             # 2e-5 ||q|| (Y8max + E8max) for the reference's roundings and d8's three, inflated the same way, and d8's own
-            # three once more because d8 is exact here; charged 3e-5 x 1.001.  sketch_keep: 4e-7 (1 + |d8| + eps) for the
+            # three once more because d8 is exact here; charged 3e-5 x 1.001.  FirstStage::out: 4e-7 (1 + |d8| + eps) for the
             # roundings of 1 - dot / -dot and of the subtraction; charged 2e-6 of the same terms.
             slack = 1.001 * eps + 3e-7 * 1.001 * qn * copy.ymax + 3e-5 * 1.001 * qn * (copy.ymax + copy.emax)
             self.lower = d8 - (slack + 2e-6 * (1.0 + np.abs(d8) + slack))

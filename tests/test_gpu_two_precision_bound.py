@@ -7,7 +7,7 @@ looser than documented, a counter that counts something else, a float16 sum that
 some chunk of pending rows (the answers stay right: the exact stage catches what a too small sum lets through, the audit
 what a too large one discards) all leave this interval, which is within 0.03 % on these inputs
 (test_two_precision_model.py asserts 1 %).  Adjacency rows are full (R = 64) so that every pair of the rows-ahead
-path and every round of sketch_range carries live edges.  Every query's answer, counters and visit order are compared
+path and every round of HalfRows::range carries live edges.  Every query's answer, counters and visit order are compared
 with the oracle's.
 
 Observed on an MI355X, 32 queries, L = 40, lower / discarded on the device / upper (discardable, met with the array
@@ -17,9 +17,9 @@ full): cosine d = 32: 38 447 / 38 449 / 38 449 (38 465, 43 120); euclidean d = 1
 (40 024, 44 504); 513 queries at d = 512 on the default dispatch: 638 674 / 638 705 / 638 776.  Every assertion's
 message carries its case's figures.
 
-Shown to bite on scratch builds (none kept): the bound doubled (sk_eps, sk_delta x 2) leaves the sandwich below
+Shown to bite on scratch builds (none kept): the bound doubled (FirstStage::eps, HalfRows::delta x 2) leaves the sandwich below
 `lower` in every case that has the stage; the float16 sums of pairs 16 .. 31 zeroed, or the second round of
-sketch_range, fail every full-row case of the path they belong to (rows of up to 384 floats; wider rows) while
+HalfRows::range, fail every full-row case of the path they belong to (rows of up to 384 floats; wider rows) while
 test_gpu_sketch.py and test_gpu_sketch_default.py (R <= 24) stay green; the carry of the maxima dropped from
 build_sketch puts the device above `upper` in test_maxima_through_every_write_path at its first small-norm append.
 """

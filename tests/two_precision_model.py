@@ -15,7 +15,7 @@ kept.  This module restates, in numpy and float64,
     lower        the same with every inflation the kernel documents charged on top, each rounded up generously.
 
 The kernel's derivation implies  lower <= discarded on the device <= upper <= discardable.  The constants of `lower`
-are the kernel's documented charges (search_kernel.h init_sketch / sketch_out, index.hip k_sketch_rows), not its output.
+are the kernel's documented charges (search_kernel.h HalfRows::query, stage_eps, FirstStage::out / HalfRows::out_l2, index.hip k_sketch_rows), not its output.
 
 Also here: the inputs the GPU tests use (`width_case`, `l_case`, `hostile_queries`, `dispatch_case`), generated through one function so that the CPU
 test (test_two_precision_model.py) checks the model's own conditions on exactly them.
@@ -160,10 +160,10 @@ class Bounds:
                 D16 = ((v16 - q16) ** 2).sum(1)
                 delta = qerr + emax
                 self.upper = D16 - 2.0 * delta * np.sqrt(D16)
-                # The kernel (sketch_out) forms D16 as ||q16||^2 + ||y16||^2 - 2 q16.y16 from three rounded sums, "error
+                # The kernel (HalfRows::out_l2) forms D16 as ||q16||^2 + ||y16||^2 - 2 q16.y16 from three rounded sums, "error
                 # below 1e-5 S" with S = ||q16||^2 + ||y16||^2 + 2 |q16.y16|, and charges 1e-5 S itself (`err`): 2e-5 S
                 # between the exact D16 and its `d16 - err`, the same above for `up`; charged here: 2.5e-5 S each way.
-                # delta: qerr, Emax and their sum carry 1.0001 each at most twice (k_sketch_rows, init_sketch): 1.0003,
+                # delta: qerr, Emax and their sum carry 1.0001 each at most twice (k_sketch_rows, HalfRows::query): 1.0003,
                 # their float32 roundings on top; charged 1.001.  root: x 1.00001 and the sqrt's rounding; charged
                 # 1.0001.  The product (1 - 2e-5); charged (1 - 4e-5).  The last line's 1e-6 (|d16| + err + delta root);
                 # charged 2e-6 of the same terms taken at their upper values, + 1e-30 for `err`'s floor.
@@ -176,10 +176,10 @@ class Bounds:
                 d16 = (1.0 - dot16) if metric == "cosine" else -dot16
                 eps = qerr * ymax + qn * emax
                 self.upper = d16 - eps
-                # init_sketch: qerr, ||q||, Emax, Ymax carry 1.0001 each and the sum another (1.0003 on every product),
+                # HalfRows::query, stage_eps: qerr, ||q||, Emax, Ymax carry 1.0001 each and the sum another (1.0003 on every product),
                 # float32 roundings on top; charged 1.001.  2e-5 ||q|| (Ymax + Emax) for the roundings of the two sums,
                 # inflated the same way, and the float16 sum's own roundings (documented below 6.6e-6 ||q|| ||y||)
-                # once more because d16 is exact here; charged 3e-5 x 1.001.  sketch_out: 4e-7 (1 + |d16| + eps) for
+                # once more because d16 is exact here; charged 3e-5 x 1.001.  FirstStage::out: 4e-7 (1 + |d16| + eps) for
                 # the roundings of 1 - dot / -dot and of the subtraction; charged 2e-6 of the same terms.
                 slack = 1.001 * eps + 3e-5 * 1.001 * qn * (ymax + emax)
                 self.lower = d16 - (slack + 2e-6 * (1.0 + np.abs(d16) + slack))

@@ -334,7 +334,7 @@ def _tp_walk(g, q, limit, sl, filters):
 
 
 def two_precision_trial(rng, device=True):
-    """One random table through the kernels that have the float16 first stage (k_greedy_search<PlainDist<NG, .., true>>,
+    """One random table through the kernels that have the float16 first stage (k_greedy_search<PlainDist<NG, .., Stage::kHalf>>,
     plain and filtered), held to the float64 models: the replays equal the oracle's walks; on the device the answers
     equal the replays, no discard is contradicted by the audit, and the number discarded lies between the models' two
     counts, taken with the maxima the device carries (every row converted since the last full conversion, deleted ones

@@ -29,12 +29,13 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # k-means kernels, the C3 build's prunes and back-edges, the exact scan, the merge) may spill at most SGPR_TIMED of
 # them; the filtered forms of the walk carry six more list pointers and get SGPR_FILTERED; everything else SGPR_ANY
 # (the run-time-length fallbacks of the quantizer kernels sit at 112 .. 135).
-# The C2 walk is the two-precision hop's (PlainDist<NG, L2, true, 4, true>, the default since SDB_TUNE_SKETCH is on),
-# with the float32 walk (PlainDist<NG, L2, true, 0, false>, the opt-out) beside it; both metrics, both timed.  Cosine / dot
-# rows of up to 384 floats walk with the int8 first stage by default (Int8Dist<NG>, SDB_TUNE_SKETCH = 3): timed too.
+# The C2 walk is the two-precision hop's (PlainDist<NG, L2, true, 4, Stage::kHalf> -- the demangled name spells the stage
+# (sdb::Stage)1 --, the default since SDB_TUNE_SKETCH is on), with the float32 walk (PlainDist<NG, L2, true, 0, (sdb::Stage)0>,
+# the opt-out) beside it; both metrics, both timed.  Cosine / dot rows of up to 384 floats walk with the int8 first stage
+# by default (Int8Dist<NG>, SDB_TUNE_SKETCH = 3): timed too.
 SGPR_TIMED, SGPR_FILTERED, SGPR_ANY = 64, 128, 160
 TIMED = re.compile(
-    r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, false|4, true)>, 2, (false|true), 8192u>"
+    r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, \(sdb::Stage\)0|4, \(sdb::Stage\)1)>, 2, (false|true), 8192u>"
     r"|k_greedy_search<sdb::Int8Dist<(1|2|3)>, 2, false, 8192u>"
     r"|k_greedy_search<sdb::BitDist<(false|true)>, "  # the bit-code walks (tools/bench_bq.py times the hamming one)
     r"|k_greedy_search_wide<(3|6), false, (8|16), (false|true)>"
@@ -86,7 +87,7 @@ def kernels(so=SO):
     for k, d in zip(out, dem):
         d = re.sub(r"\s*\[clone .*\]$", "", d)
         d = re.sub(r"^void ", "", d)
-        d = re.sub(r"\(.*\)$", "", d)  # drop the parameter list
+        d = re.sub(r"\([^()]*\)$", "", d)  # drop the parameter list (a template argument may hold parentheses of its own)
         row = {"kernel": d}
         for f in FIELDS:
             row[f[1:]] = int(k.get(f, "0"))
@@ -130,7 +131,7 @@ def markdown(rows):
 
 # the kernels DESIGN.md's register table shows: what the BASELINE configurations launch in their timed regions
 DESIGN = re.compile(
-    r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, false|4, true)>, 2, false, 8192u>"
+    r"^sdb::(k_greedy_search<sdb::PlainDist<(3|6), (false|true), true, (0, \(sdb::Stage\)0|4, \(sdb::Stage\)1)>, 2, false, 8192u>"
     r"|k_greedy_search<sdb::Int8Dist<3>, 2, false, 8192u>"
     r"|k_greedy_search_wide<3, false, (8|16), false>|k_greedy_search_pq2<4294967295u>"
     r"|k_greedy_search_pqw<15, 33, 4294967295u, 4, 15, true>|k_pq_lut_t<true, (3, 96|0, 4)>|k_pq_encode_t<true, 3, true>"
