@@ -325,3 +325,45 @@ def test_new_node_prune_tiled_and_untiled_agree(oracle, metric, d, n, R, L, sear
             # rows wider than 4 KB leave no room for a useful tile: those dimensions keep the one-wave kernel
             assert (st["staged_rows"] > 0) == (no_tile != 1 and d <= 1024)
             ix.close()
+
+
+@pytest.mark.parametrize("round_size", [0, 64])
+def test_batched_build_under_a_small_hash_limit(oracle, round_size):
+    """The build's searches keep their visited sets in the same LDS tables and pass the index's hash_limit on
+    (build.hip): with the limit at 24 every insert's walk spills within its first hops, at 150 the walks of the
+    build's second half spill mid-walk, at 300 only the longest walks of the last rounds do, within their last marks --
+    while they write their visit logs and the pair-distance cache on both sides of the spill.  (A walk over the
+    finished graph marks 243 .. 323 ids: asserted below on the oracle's walks.)  n = 1 500 keeps every round below 512
+    points, which the workgroup-per-query walk takes; wide_walk = 1 sends the same rounds through the one-wave walk.  The graph equals the oracle's restatement of the schedule edge for edge, and with the limit back at its
+    default the searches on it are the oracle's."""
+    from tests.helpers import assert_same_graph
+    metric, d, n, R, L = "cosine", 48, 1500, 24, 40
+    rng = np.random.default_rng(d + n + round_size)
+    lat = rng.standard_normal((8, d)).astype(np.float32)
+    base = rng.standard_normal((n, 8)).astype(np.float32) @ lat + 0.15 * rng.standard_normal((n, d)).astype(np.float32)
+    base = (base / np.linalg.norm(base, axis=1, keepdims=True)).astype(np.float32)
+    sv = start_vector(np.random.default_rng(3), d)
+    o = oracle.Index(d, metric, R, L, 1.2, impl=oracle.IMPL_AVX2 if oracle.has_avx2() else oracle.IMPL_ASM)
+    o.set_start(sv)
+    ids = np.arange(2, n + 2, dtype=np.uint64)
+    assert o.insert_rounds(ids, base, round_size=round_size) == 0
+    q = (base[rng.integers(0, n, 32)] + 0.05 * rng.standard_normal((32, d))).astype(np.float32)
+    want = [o.search(q[i], 10, L) for i in range(32)]
+    # the condition of the case: every walk over the finished graph passes 150 marks, some pass 300
+    marks = [w[3].n_dist for w in want]
+    assert min(marks) > 150 + 64 and max(marks) > 300 + 1, (min(marks), max(marks))
+    for hash_limit in (24, 150, 300):
+        for wide_walk in (0, 1):
+            ix = _new_gpu(d, metric, R, L)
+            ix.set_tuning("hash_limit", hash_limit)
+            ix.set_tuning("wide_walk", wide_walk)
+            ix.set_start(sv)
+            ix.insert_batch(ids, base, round_size=round_size)
+            assert_same_graph(ix, o)
+            ix.set_tuning("hash_limit", 0)
+            g_ids, g_d, g_c, tr = ix.search_batch(q, 10, L, trace=True, visit_cap=512)
+            for i, (o_ids, o_d, o_vis, o_tr) in enumerate(want):
+                assert int(g_c[i]) == len(o_ids) and np.array_equal(g_ids[i, :len(o_ids)], o_ids) and np.array_equal(bits(g_d[i, :len(o_ids)]), bits(o_d))
+                assert (int(tr.n_dist[i]), int(tr.n_hop[i])) == (o_tr.n_dist, o_tr.n_hop)
+                assert np.array_equal(tr.visit_ids[i, :o_tr.n_hop], o_vis)
+            ix.close()

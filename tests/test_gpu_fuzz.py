@@ -38,6 +38,7 @@ def test_fuzz_short_soak(oracle, monkeypatch, seed):
         fz.merge_trial(rng)
         fz.pq_trial(rng)
         fz.flat_trial(rng)
-        fz.trial(rng, t)
-        # (a stream of its own: the four trials above draw what they drew before this one existed)
-        fz.two_precision_trial(np.random.default_rng([seed, t, 2]))
+        fz.trial(rng, t, fz.spill_generator(seed, t))
+        # (streams of their own: the four trials above draw what they drew before this one, and the repeats under a
+        # lowered hash_limit, existed)
+        fz.two_precision_trial(np.random.default_rng([seed, t, 2]), spill_rng=fz.spill_generator(seed, t))

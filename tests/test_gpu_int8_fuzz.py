@@ -25,6 +25,6 @@ def _fuzz():
 def test_int8_trials(oracle, seed):
     fz = _fuzz()
     for t in range(TRIALS):
-        out = fz.int8_trial(np.random.default_rng([seed, t, 3]))
+        out = fz.int8_trial(np.random.default_rng([seed, t, 3]), spill_rng=fz.spill_generator(seed, t))
         for b in out["batches"]:
             assert b is None or b[0] <= b[1] <= b[2], (out["desc"], b)

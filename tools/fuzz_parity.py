@@ -8,6 +8,11 @@ Every trial also draws a table for the two-precision hop (two_precision_trial): 
 first stage, plain and filtered, against the float64 models of tests/two_precision_model.py and
 tests/filtered_two_precision_model.py -- answers, and the number of neighbours discarded between the models' two counts.
 
+Every kind of index trial also repeats search batches it has already compared under a lowered hash_limit (24, 200 or
+1000, drawn from a generator of its own so that every other draw stays what it was): the LDS visited sets spill to
+their bitsets mid-walk, and the answers -- for the two-precision walks also the discarded counts -- must be bit for bit
+those of the run at the default limit.
+
   python tools/fuzz_parity.py --trials 200 --seed 1      (prints one JSON line; exit code 1 on the first mismatch)
 """
 import argparse
@@ -66,7 +71,27 @@ def compare_exact(g, o, q, metric, tag):
     assert (k1[:, -1] == np.finfo(np.float32).max).all(), (tag, "K1 unknown id")
 
 
-def compare_searches(rng, g, o, d, kind, L, live, tag, metric=None):
+SPILL_LIMITS = (24, 200, 1000)
+
+
+def spill_generator(seed, t):
+    """the stream the lowered limits are drawn from: its own, next to [seed, t] (the trials), [seed, t, 2] (the
+    two-precision trial) and [seed, t, 3] (the int8 trial)"""
+    return np.random.default_rng([seed, t, 7])
+
+
+def same_call(a, b, tag):
+    """two calls of one batch: ids, distance bits, counts, n_dist / n_hop / n_edges and the visit logs up to n_hop"""
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2]), (tag, "ids / counts")
+    assert _tp_same_bits(a[1], b[1]), (tag, "dist bits")
+    for x, y in ((a[3].n_dist, b[3].n_dist), (a[3].n_hop, b[3].n_hop), (a[3].n_edges, b[3].n_edges)):
+        assert np.array_equal(x, y), (tag, "counters")
+    for i in range(a[0].shape[0]):
+        h = int(b[3].n_hop[i])
+        assert np.array_equal(a[3].visit_ids[i, :h], b[3].visit_ids[i, :h]), (tag, "visit order", i)
+
+
+def compare_searches(rng, g, o, d, kind, L, live, tag, metric=None, spill_rng=None):
     nq = 12
     q = draw_rows(rng, nq, d, kind)
     if metric is not None and len(live) >= 1:
@@ -81,6 +106,15 @@ def compare_searches(rng, g, o, d, kind, L, live, tag, metric=None):
         assert np.array_equal(bits(d_g[i, :len(o_ids)]), bits(o_d)), (tag, "dist bits", i)
         assert int(tr.n_dist[i]) == o_tr.n_dist and int(tr.n_hop[i]) == o_tr.n_hop, (tag, "counters", i)
         assert np.array_equal(tr.visit_ids[i, :o_tr.n_hop], o_vis), (tag, "visit order", i)
+    if spill_rng is not None:
+        # the batch just compared, once more with visited sets that give up early: the default dispatch and the one-wave walk
+        limit = int(spill_rng.choice(SPILL_LIMITS))
+        g.set_tuning("hash_limit", limit)
+        for mode in (0, 1):
+            g.set_tuning("wide_walk", mode)
+            same_call(g.search_batch(q, k, sl, trace=True, visit_cap=2048), (ids_g, d_g, c_g, tr), (tag, "hash_limit %d" % limit, "wide_walk %d" % mode))
+        g.set_tuning("wide_walk", 0)
+        g.set_tuning("hash_limit", 0)
     if len(live) >= 4:
         filters = []
         for i in range(nq):
@@ -135,7 +169,7 @@ def check_graph(g, o):
     assert g.version_diff() == 0, "graph versions differ after a committed write"
 
 
-def trial(rng, t):
+def trial(rng, t, spill_rng=None):
     d = int(rng.choice(DIMS))
     metric = str(rng.choice(METRICS))
     kind = str(rng.choice(["unit", "latent", "grid", "dups"], p=[0.35, 0.35, 0.15, 0.15]))
@@ -170,7 +204,7 @@ def trial(rng, t):
             g.insert_batch(ids, base, round_size=1)
         check_graph(g, o)
         live = [int(v) for v in ids]
-        compare_searches(rng, g, o, d, kind, L, live, "after build", metric)
+        compare_searches(rng, g, o, d, kind, L, live, "after build", metric, spill_rng)
         quantized = False
         for step in range(int(rng.integers(1, 4))):
             if not quantized and d >= 4 and rng.integers(0, 3) == 0:
@@ -189,7 +223,7 @@ def trial(rng, t):
                         vs.attach(g, gpq, o_ids, gcodes)
                         quantized = True
                         desc["pq"] = CURRENT["pq"] = [M, Kc]
-                        compare_searches(rng, g, o, d, kind, L, live, "after attach")
+                        compare_searches(rng, g, o, d, kind, L, live, "after attach", None, spill_rng)
             n_del = int(rng.integers(0, max(1, len(live) // 4)))
             dels = [int(v) for v in rng.choice(live, size=n_del, replace=False)] if n_del else []
             rest = [v for v in live if v not in set(dels)]
@@ -297,7 +331,7 @@ def trial(rng, t):
                 g.compact()
                 assert g.row_usage()[1] == 0
             check_graph(g, o)
-            compare_searches(rng, g, o, d, kind, L, live, "after write batch %d" % step, None if quantized else metric)
+            compare_searches(rng, g, o, d, kind, L, live, "after write batch %d" % step, None if quantized else metric, spill_rng)
     finally:
         g.close()
     return desc
@@ -333,7 +367,7 @@ def _tp_walk(g, q, limit, sl, filters):
     return ans, d1 - d0, c1 - c0, in_use
 
 
-def two_precision_trial(rng, device=True):
+def two_precision_trial(rng, device=True, spill_rng=None):
     """One random table through the kernels that have the float16 first stage (k_greedy_search<PlainDist<NG, .., Stage::kHalf>>,
     plain and filtered), held to the float64 models: the replays equal the oracle's walks; on the device the answers
     equal the replays, no discard is contradicted by the audit, and the number discarded lies between the models' two
@@ -341,7 +375,8 @@ def two_precision_trial(rng, device=True):
     included).  The routing is stated here, not imported: the stage runs when the width has it, no quantizer is attached
     (none is, here), no transaction is open, and searchSize <= 96 for a plain call / <= 128 for a filtered one -- on the
     one-wave kernel, which wide_walk = 1 selects at every batch size and the default dispatch only where the many-waves
-    kernel is out (a filtered call with searchSize > 96).  device=False: everything except the device.
+    kernel is out (a filtered call with searchSize > 96).  spill_rng: each batch's plain and filtered walk once more under
+    a lowered hash_limit -- the same answers and the same discarded counts.  device=False: everything except the device.
     Returns {"desc": .., "batches": [{"stage", "plain": (lower, discarded, upper), "filtered": (..)}]}."""
     from tests import filtered_two_precision_model as F
     from tests import two_precision_model as M
@@ -436,11 +471,13 @@ def two_precision_trial(rng, device=True):
         if with_bitmaps:
             forms.append(("filtered", vamana.FilterBitmaps.from_sets(filters, align=int(rng.choice([1, 64]))), reps_f, t_f))
         g.set_tuning("wide_walk", 1)
+        kept = {}
         for walk, fl, reps, t in [("plain", None, reps_p, t_p)] + forms:
             seen = []
             for mode in (2, 1):
                 g.set_tuning("sketch", mode)
                 ans, discarded, contradicted, in_use = _tp_walk(g, q, limit, sl, fl)
+                kept.setdefault((walk, mode), (fl, ans, discarded))
                 what = (tag, walk, "bitmaps" if isinstance(fl, vamana.FilterBitmaps) else "", "sketch=%d" % mode,
                         "lower %d / discarded on the device %d / upper %d, contradicted %d" % (t.lower, discarded, t.upper, contradicted))
                 assert in_use == (not no_stage), what
@@ -453,6 +490,17 @@ def two_precision_trial(rng, device=True):
                 seen.append(discarded)
             assert seen[0] == seen[1], (tag, walk, "the audit run discarded %d, the plain run %d" % tuple(seen))
             rec[walk][1] = seen[1]
+        if spill_rng is not None:
+            # the same walks with visited sets that spill mid-walk: where the set lives decides no answer and no discard
+            low = int(spill_rng.choice(SPILL_LIMITS))
+            g.set_tuning("hash_limit", low)
+            for (walk, mode), (fl, ans0, discarded0) in kept.items():
+                g.set_tuning("sketch", mode)
+                ans, discarded, contradicted, _ = _tp_walk(g, q, limit, sl, fl)
+                what = (tag, walk, "sketch=%d" % mode, "hash_limit %d" % low)
+                same_call(ans, ans0, what)
+                assert contradicted == 0 and discarded == discarded0, what + ("discarded %d, %d at the default limit" % (discarded, discarded0),)
+            g.set_tuning("hash_limit", 0)
         # the default dispatch: 32 queries are the many-waves kernel's (no stage) wherever it can take them, which is
         # searchSize <= 96; beyond, a plain call is the bitset kernel's and a filtered one keeps the hop
         g.set_tuning("wide_walk", 0)
@@ -572,13 +620,14 @@ def two_precision_sums(results):
 INT8_WIDTHS = (32, 64, 96, 128, 160, 256, 320, 352, 384)
 
 
-def int8_trial(rng, device=True):
+def int8_trial(rng, device=True, spill_rng=None):
     """One random cosine / dot table of a width that has the int8 first stage (SDB_TUNE_SKETCH = 3, the default; 4 with
     audit), through the one-wave walk: the replays equal the oracle's walks; on the device the answers equal the replays
     under knobs 4, 3, 1 and 0, no discard is contradicted, and -- while the float64 model (tests/int8_stage_model.py) keeps
     the int8 copy, with the scale and the maxima carried as the index carries them -- the number discarded lies between
     the model's two counts.  A table the model refuses the copy (rows far below the table's scale) walks with the float16
-    copy: answers and audit only.  Returns {"desc": .., "batches": [(lower, discarded, upper) or None]}."""
+    copy: answers and audit only.  spill_rng: each batch once more under a lowered hash_limit, knob by knob -- the same
+    answers and the same discarded counts.  Returns {"desc": .., "batches": [(lower, discarded, upper) or None]}."""
     from tests import int8_stage_model as M8
     from tests import two_precision_model as M
     d = int(rng.choice(INT8_WIDTHS))
@@ -627,11 +676,18 @@ def int8_trial(rng, device=True):
         out["batches"].append(rec)
         if not device:
             return
+        low = int(spill_rng.choice(SPILL_LIMITS)) if spill_rng is not None else 0
         for mode in (4, 3, 1, 0):
             if state["refused"] and mode in (4, 3):
                 continue  # (setting the knob would ask for the int8 copy again: the table is left with what it holds)
             g.set_tuning("sketch", mode)
             ans, discarded, contradicted, in_use = _tp_walk(g, q, limit, sl, None)
+            if low:  # the visited sets spill mid-walk: the same answers, the same discards
+                g.set_tuning("hash_limit", low)
+                again, discarded_low, contradicted_low, _ = _tp_walk(g, q, limit, sl, None)
+                g.set_tuning("hash_limit", 0)
+                same_call(again, ans, (tag, "sketch=%d" % mode, "hash_limit %d" % low))
+                assert contradicted_low == 0 and discarded_low == discarded, (tag, "sketch=%d" % mode, "hash_limit %d: discarded %d, %d at the default limit" % (low, discarded_low, discarded))
             what = (tag, "sketch=%d" % mode, "lower %d / discarded on the device %d / upper %d, contradicted %d" % (t.lower, discarded, t.upper, contradicted))
             assert in_use == (mode != 0) and contradicted == 0, what
             _tp_equals_replay(ans, reps, what)
@@ -901,10 +957,10 @@ def main():
             t3 = time.time()
             if a.verbose:
                 print("trial %d: index %s" % (t, CURRENT), file=sys.stderr, flush=True)
-            desc = trial(rng, t)
+            desc = trial(rng, t, spill_generator(a.seed, t))
             if a.verbose:
                 print("trial %d: two-precision" % t, file=sys.stderr, flush=True)
-            two_precision.append(two_precision_trial(np.random.default_rng([a.seed, t, 2])))  # (a stream of its own)
+            two_precision.append(two_precision_trial(np.random.default_rng([a.seed, t, 2]), spill_rng=spill_generator(a.seed, t)))  # (streams of their own)
             if time.time() - t1 > 20:
                 print("slow trial %d: merge %.1fs, pq %.1fs %s, index %.1fs %s" % (
                     t, t2 - t1, t3 - t2, pq_desc, time.time() - t3, CURRENT), file=sys.stderr)
