@@ -18,8 +18,8 @@ namespace sdb {
 // hammingDistance / jaccardDistance (distance.go:45-67) of two codes of W words -- the one home of the counts, of the
 // jaccard rounding (one float32 division, one subtraction) and of the empty-union rule.  Hamming: s = |x ^ y|;
 // jaccard: s = |x & y|, u = |x | y|.  VEC2: W is even and y sits on a 16-byte boundary, two words per load.
-template <bool JACCARD, bool VEC2 = false>
-__device__ __forceinline__ float bit_pair_dist(const uint64_t *x, const uint64_t *__restrict__ y, uint32_t W) {
+template <bool JACCARD, bool VEC2 = false, class XP>  // XP: pointer to the query's words, in any address space
+__device__ __forceinline__ float bit_pair_dist(XP x, const uint64_t *__restrict__ y, uint32_t W) {
   typedef unsigned long long word2 __attribute__((ext_vector_type(2)));
   uint32_t s = 0, u = 0;
   if constexpr (VEC2) {

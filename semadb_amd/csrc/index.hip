@@ -657,10 +657,11 @@ int launch_greedy_search(const SearchArgs &a_in, uint32_t nq, hipStream_t stream
     }
     if (search_uses_hash(a, nq)) {
       // up to 2^24 rows: the 16-bit-cell set (16 KB, six walks per CU); beyond: 32-bit cells
-      if ((uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash) return launch_nreg<PQDist, kHash16>(a, nq, stream, lds);
-      return launch_nreg<PQDist, kHashCapPQ>(a, nq, stream, lds);
+      if ((uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash)
+        return a.pq_lut_in_lds ? launch_nreg<PQLdsDist, kHash16>(a, nq, stream, lds) : launch_nreg<PQGlobalDist, kHash16>(a, nq, stream, lds);
+      return a.pq_lut_in_lds ? launch_nreg<PQLdsDist, kHashCapPQ>(a, nq, stream, lds) : launch_nreg<PQGlobalDist, kHashCapPQ>(a, nq, stream, lds);
     }
-    return launch_nreg<PQDist, 0>(a, nq, stream, lds);
+    return a.pq_lut_in_lds ? launch_nreg<PQLdsDist, 0>(a, nq, stream, lds) : launch_nreg<PQGlobalDist, 0>(a, nq, stream, lds);
   }
   if (a.metric == SDB_METRIC_EUCLIDEAN) return launch_ng<true>(a, nq, stream);
   return launch_ng<false>(a, nq, stream);

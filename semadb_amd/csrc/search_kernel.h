@@ -21,6 +21,7 @@
 #include "bq.h"
 #include "dist_core.h"
 #include "index.h"
+#include <type_traits>
 
 namespace sdb {
 
@@ -127,13 +128,26 @@ struct ChunkPairs {
 // The kernel's own arguments once more, through a pointer the optimiser cannot see through.  Every walk kernel takes
 // its SearchArgs by value as its first parameter, i.e. at offset 0 of the kernarg segment; a field read through `a` is
 // loaded in the kernel's first instructions and -- with ~60 fields against ~100 SGPRs -- parked in a VGPR lane until it
-// is used.  A field that only the epilogue reads is read through this view: one scalar load at the point of use.
-__device__ __forceinline__ const SearchArgs &cold_args(const SearchArgs &) {
-  typedef const __attribute__((address_space(4))) SearchArgs *kernarg_view;
-  uintptr_t p = (uintptr_t)(kernarg_view)__builtin_amdgcn_kernarg_segment_ptr();
+// is used.  A field that only the hop's stage or the epilogue reads is read through this view: one scalar load
+// (s_load_dword*) at the point of use.  The view keeps the kernarg segment's address space (constant, 4): laundered
+// into a generic pointer, as it once was, every field read became a vector flat_load of a uniform address behind a
+// full s_waitcnt, and every pointer read through it a generic one (flat loads, stores and atomics).  A pointer field
+// read through the view is generic by its declared type; as_global() says what it is -- device memory -- before it
+// is dereferenced (tests/test_stage_load_schedule.py: no flat_ instruction in any walk kernel).
+typedef const __attribute__((address_space(4))) SearchArgs ColdArgs;
+__device__ __forceinline__ ColdArgs &cold_args(const SearchArgs &) {
+  uintptr_t p = (uintptr_t)(ColdArgs *)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(p));
-  return *(const SearchArgs *)p;
+  return *(ColdArgs *)p;
 }
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(1))) T *as_global(T *p) {
+  return (__attribute__((address_space(1))) T *)p;
+}
+// 1, 2 or 3 dwords of device memory at a 4-byte-aligned address, one load instruction
+typedef uint32_t gwords2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t gwords3 __attribute__((ext_vector_type(3), aligned(4)));
+typedef const __attribute__((address_space(1))) char *gbytes;  // a byte address in device memory
 
 __device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
@@ -275,7 +289,7 @@ struct HalfRows {
   // rounding; the final 1 - dot / -dot and the subtraction of the bound are covered per comparison (FirstStage::out).  A
   // query or a table with a non-finite or float16-overflowing element makes the bound infinite or NaN: nothing is
   // discarded then.
-  __device__ __forceinline__ void query(const float4 (&xq)[NG], int lane, const SearchArgs &c, float &qerr, float &qn) {
+  __device__ __forceinline__ void query(const float4 (&xq)[NG], int lane, ColdArgs &c, float &qerr, float &qn) {
     float e2 = 0.0f, n2 = 0.0f;
 #pragma unroll
     for (int g = 0; g < NG; g++) {
@@ -303,9 +317,12 @@ struct HalfRows {
       delta = (qerr + c.sk_emax) * 1.0001f;
     }
   }
-  static __device__ __forceinline__ void load(row_t &y, const char *r) {
+  static __device__ __forceinline__ void load(row_t &y, gbytes r) {
 #pragma unroll
-    for (int g = 0; g < NG; g++) y.g[g] = *reinterpret_cast<const uint2 *>(r + g * 256);
+    for (int g = 0; g < NG; g++) {
+      const gwords2 p = *(const __attribute__((address_space(1))) gwords2 *)(r + g * 256);
+      y.g[g] = make_uint2(p.x, p.y);
+    }
   }
   __device__ __forceinline__ float partial(const row_t &y) const {
     float acc = 0.0f;
@@ -337,7 +354,7 @@ struct HalfRows {
   // takes the writes of the lanes that hold no result
   __device__ __forceinline__ void range(const SearchArgs &a, const uint32_t *s_slot, float *s_res, float *dump, int cnt, int lane) const {
     const int L = lane & 31, half = lane >> 5;
-    const char *baseL = static_cast<const char *>(cold_args(a).sketch) + L * kLaneBytes;
+    const gbytes baseL = as_global(static_cast<const char *>(cold_args(a).sketch)) + L * kLaneBytes;
     const uint32_t row_bytes = a.ld * kElemBytes;
     for (int c0 = 0; c0 < cnt; c0 += 2 * kRound) {
       const int m = cnt - c0 < 2 * kRound ? cnt - c0 : 2 * kRound;
@@ -391,7 +408,7 @@ struct Int8Rows {
   uint32_t qa[NG], qb[NG];  // four int8 each, in xq's element order
   float scale;              // s s_q / 128
 
-  __device__ __forceinline__ void query(const float4 (&xq)[NG], int lane, const SearchArgs &c, float &qerr, float &qn) {
+  __device__ __forceinline__ void query(const float4 (&xq)[NG], int lane, ColdArgs &c, float &qerr, float &qn) {
     float mx = 0.0f;
 #pragma unroll
     for (int g = 0; g < NG; g++)
@@ -420,11 +437,16 @@ struct Int8Rows {
     qn = __builtin_sqrtf(n2) * 1.0001f, qerr = __builtin_sqrtf(e2) * 1.0001f + 2e-7f * qn;
     scale = c.sk8_scale * sq128;
   }
-  static __device__ __forceinline__ void load(row_t &y, const char *r) {
-    struct __attribute__((packed, aligned(4))) RowWords { uint32_t w[NG]; };
-    const RowWords p = *reinterpret_cast<const RowWords *>(r);
-#pragma unroll
-    for (int g = 0; g < NG; g++) y.w[g] = p.w[g];
+  static __device__ __forceinline__ void load(row_t &y, gbytes r) {
+    if constexpr (NG == 1) {
+      y.w[0] = *(const __attribute__((address_space(1))) uint32_t *)r;
+    } else if constexpr (NG == 2) {
+      const gwords2 p = *(const __attribute__((address_space(1))) gwords2 *)r;
+      y.w[0] = p.x, y.w[1] = p.y;
+    } else {
+      const gwords3 p = *(const __attribute__((address_space(1))) gwords3 *)r;
+      y.w[0] = p.x, y.w[1] = p.y, y.w[2] = p.z;
+    }
   }
   __device__ __forceinline__ int partial(const row_t &y) const {
     int sa = 0, sb = 0;
@@ -468,8 +490,9 @@ __device__ __forceinline__ float stage_eps(float qerr, float qn, float ymax, flo
 }
 
 // A float32-only walk carries no stage state.  (Held as a plain one-byte member, not [[no_unique_address]] and not an empty
-// base: either moves Int8Dist's members and costs its NG = 3 kernel a VGPR, 229 for 228; a stage as a base in front of xq
-// measured 235.)
+// base: when the int8 walk at NG = 3 took 228 VGPRs, either moved Int8Dist's members and cost it one, 229, and a stage as
+// a base in front of xq measured 235.  Re-measured with the hop's loads issued in every hop, 184 VGPRs:
+// [[no_unique_address]] makes no difference any more; the layout is left as it was.)
 struct NoStage {};
 
 template <class Fmt, bool L2, bool AHEAD>
@@ -480,36 +503,45 @@ struct FirstStage {
   float eps;  // stage_eps of this query
   // Rows of up to 384 floats (stage_ahead): the copy rows of ALL 64 edges of an adjacency row fit the register file, so
   // they are asked for as soon as the edge ids are there -- BEFORE the visited-set test, whose LDS round trips (~2 100
-  // cycles) then run under the rows' flight instead of in front of it.  Rows of edges that turn out to be visited already
-  // were read for nothing (a quarter more copy bytes; the walk is not bound by bytes).  (Asking after the test,
-  // compacted, was the measured alternative and lost; HISTORY.md keeps the figures.)
+  // cycles) then run under the rows' flight instead of in front of it.  That only happens if nothing between the loads
+  // and the test waits for them: the loads are global loads (the copy's address is typed as device memory; as flat loads
+  // they could only be drained whole, and were, in front of the test), they are issued in every hop, not only with the
+  // array full (registers that are loaded on one side of a branch are copied into place, with a wait, on that side),
+  // and the first wait on them is the counted one in front of the first sum (tests/test_stage_load_schedule.py reads
+  // all of this from the built library).  Rows of edges that turn out to be visited already were read for nothing (a
+  // quarter more copy bytes; the walk is not bound by bytes), and so are the rows of the hops before the array is full
+  // (at searchSize 75 the first two hops of about 79).  (Asking after the test, compacted, was the measured alternative
+  // and lost; HISTORY.md keeps the figures.)
   bool loaded = false;
   row_t y[AHEAD ? 32 : 1];  // pair u: edge 2u (lanes 0..31) and edge 2u + 1 (lanes 32..63); (kept last: with the rows in
-                            // front of the flag the int8 walk at NG = 3 takes 233 registers for 228)
+                            // front of the flag the int8 walk at NG = 3 took 233 registers for 228; at today's 184 the
+                            // order makes no difference, re-measured)
 
   template <int NG>
   __device__ __forceinline__ void init(const SearchArgs &a, const float4 (&xq)[NG], int lane) {
-    const SearchArgs &c = cold_args(a);  // (what only the hop reads: through the opaque view, not parked in SGPRs)
+    ColdArgs &c = cold_args(a);  // (what only the hop reads: through the opaque view, not parked in SGPRs)
     float qerr, qn;
     fmt.query(xq, lane, c, qerr, qn);
     eps = stage_eps(qerr, qn, c.sk_ymax, c.sk_emax);
   }
 
-  // A hop asks for its copy rows ahead with the array full.  The walk is launched only with the copy (index.hip
-  // launch_plain), so the pointer need not be tested -- and untested, the compiler sees that keep()'s compacting path is
-  // never taken with the rows asked for ahead: 87 -> 14 spilled SGPRs at NG = 3 (cosine / dot).  The euclidean walk keeps
-  // the test (through the opaque view): untested, this compiler spills 4 VGPRs there; tested, none.
+  // A hop asks for its copy rows ahead; `loaded` says whether keep() may use them (the array is full).  The walk is
+  // launched only with the copy (index.hip launch_plain), so the pointer need not be tested -- and untested, the compiler
+  // sees that keep()'s compacting path is never taken with the rows asked for ahead: 87 -> 14 spilled SGPRs at NG = 3
+  // (cosine / dot).  The euclidean walk keeps the test (through the opaque view) in front of its loads: untested, this
+  // compiler spills 4 VGPRs there; tested, none.
   __device__ __forceinline__ void begin(const SearchArgs &a, uint32_t nb, bool valid, bool full) {
     if constexpr (AHEAD) {
       loaded = false;
-      if constexpr (L2) full = full && cold_args(a).sketch != nullptr;
-      if (!full) return;
+      if constexpr (L2)
+        if (cold_args(a).sketch == nullptr) return;
       const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
       const int L = lane & 31;
       const bool hi = lane >= 32;
-      // (the copy's addresses through the opaque view at each use: one scalar load, where arguments that live through
-      // the walk would hold SGPR pairs spilled into VGPR lanes -- tools/kernel_table.py)
-      const char *baseL = static_cast<const char *>(cold_args(a).sketch) + L * Fmt::kLaneBytes;
+      // (the copy's addresses through the opaque view at each use: one scalar load, in flight beside the adjacency
+      // row's, where arguments that live through the walk would hold SGPR pairs spilled into VGPR lanes --
+      // tools/kernel_table.py)
+      const gbytes baseL = as_global(static_cast<const char *>(cold_args(a).sketch)) + L * Fmt::kLaneBytes;
       const uint32_t row_bytes = a.ld * Fmt::kElemBytes;
       const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
 #pragma unroll
@@ -517,8 +549,8 @@ struct FirstStage {
         const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
         Fmt::load(y[u], baseL + (uint64_t)(hi ? s1 : s0) * row_bytes);
       }
-      if constexpr (L2) fmt.yy = cold_args(a).sketch_norm[safe];
-      loaded = true;
+      if constexpr (L2) fmt.yy = as_global(cold_args(a).sketch_norm)[safe];
+      loaded = full;
     }
   }
 
@@ -558,7 +590,7 @@ struct FirstStage {
       const bool mine = (pend >> lane) & 1ull;
       float yy_me = 0.0f;
       if constexpr (L2)
-        if (mine) yy_me = cold_args(a).sketch_norm[nb];  // (in flight while the rows are summed)
+        if (mine) yy_me = as_global(cold_args(a).sketch_norm)[nb];  // (in flight while the rows are summed)
       const uint32_t rank =
           __builtin_amdgcn_mbcnt_hi((uint32_t)(pend >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pend, 0u));
       uint32_t *s_slot = hs;
@@ -1035,7 +1067,7 @@ struct PlainWideDist : PlainDist<NG, L2, true, WidePairs<NG, W, L2>::value> {
 
   // ---- waves 1 .. W-1
   // a computing wave's share of the distances to the neighbours of the candidate ahead
-  __device__ __forceinline__ void compute_ahead(const SearchArgs &a, const uint32_t *rowp, int lane) {
+  __device__ __forceinline__ void compute_ahead(const SearchArgs &a, const __attribute__((address_space(1))) uint32_t *rowp, int lane) {
     const uint32_t nb = rowp[lane];
     const uint64_t m = __ballot(nb != kNoSlot);
     const int deg = __popcll(m);  // rows are padded with kNoSlot behind their edges
@@ -1095,7 +1127,7 @@ struct PlainWideDist : PlainDist<NG, L2, true, WidePairs<NG, W, L2>::value> {
 #ifdef SDB_STAMPS
       hs_n++;
 #endif
-      const uint32_t *ahead = reinterpret_cast<const uint32_t *>(sh->ahead);
+      const auto *ahead = as_global(reinterpret_cast<const uint32_t *>(sh->ahead));  // (an adjacency row: device memory)
       if (kFirstAhead == 2 && wave == 1) {
         if (sh->mark_on) {
           const uint32_t nb = ahead[lane];
@@ -1122,29 +1154,50 @@ struct PlainWideDist : PlainDist<NG, L2, true, WidePairs<NG, W, L2>::value> {
 
 // Fitted product quantizer: dist = sum_i lut[i*K + code_i], plain fp32 adds in index order
 // (product.go:271-275).  One lane per neighbour: all new neighbours of a hop in one pass.
-struct PQDist {
+// IN_LDS: the query's table was copied into LDS (SearchArgs::pq_lut_in_lds), else it is read where k_pq_lut left it.  Two
+// kernels and a pointer typed by its address space, not one kernel and a generic pointer: through a generic pointer every
+// lookup is a flat load, which counts on both wait counters (tests/test_stage_load_schedule.py).
+template <bool IN_LDS, bool OPAQUE_K = false>
+struct PQDistT {
   static constexpr Stage kStage = Stage::kNone;
   // (the same naming of the next hop's row, with its code rows fetched ahead: 0.419 against 0.359 ms per batch at
   // 4M x 768, M = 8 -- a one-wave hop is bound by its instruction count, not by the fetch; measured and removed)
   static constexpr bool kSpeculate = false;
   static constexpr bool kHasStamps = false;
   static constexpr bool kPointDistances = false;  // LUT distance != the centroid-pair distance of the prunes
-  const float *lut;  // this query's [M][K] table, in LDS or in global memory
+  // K, the table's row stride.  OPAQUE_K (the one-wave walk with its table in LDS): read through a value the optimiser
+  // cannot see through, so that the rows' offsets k K are computed where they are used.  Known to be loop-invariant
+  // they are hoisted out of the walk, one SGPR each for the up to 32 rows of a lookup, and parked in VGPR lanes: 139
+  // spilled SGPRs on the filtered kernel (limit 128), 82 so.  (Seen with the clang of ROCm's LLVM this library is built
+  // with, AMD clang 22.0.0git of ROCm 7.2.0; when a compiler keeps the filtered PQLdsDist kernels under the limit of
+  // tools/kernel_table.py --check without it, the barrier can go.)
+  static __device__ __forceinline__ uint32_t row_stride(const SearchArgs &a) {
+    uint32_t K = a.pq_K;
+    if constexpr (OPAQUE_K) asm volatile("" : "+s"(K));
+    return K;
+  }
+  typedef const __attribute__((address_space(3))) float *lds_table;
+  typedef const __attribute__((address_space(1))) float *global_table;
+  typename std::conditional<IN_LDS, lds_table, global_table>::type lut;  // this query's [M][K] table
+  __device__ __forceinline__ void table_in_lds(const float *lds) {
+    static_assert(IN_LDS, "a table in LDS");
+    lut = (lds_table)lds;
+  }
   __device__ __forceinline__ void init(const SearchArgs &a, uint32_t q, int lane, float *lds) {
-    const float *g = a.pq_lut + (size_t)q * a.pq_M * a.pq_K;
-    if (a.pq_lut_in_lds) {
-      for (uint32_t i = lane; i < a.pq_M * a.pq_K; i += 64) lds[i] = g[i];
+    const float *g = a.pq_lut + (size_t)q * a.pq_M * row_stride(a);
+    if constexpr (IN_LDS) {
+      for (uint32_t i = lane; i < a.pq_M * row_stride(a); i += 64) lds[i] = g[i];
       __syncthreads();
-      lut = lds;
+      lut = (lds_table)lds;
     } else {
-      lut = g;
+      lut = as_global(g);
     }
   }
   // dist = 0; dist += lut[i][code_i] for i = 0 .. M-1, plain fp32 adds in index order (product.go:271-275), over the
   // code row at `c` (M bytes; rows are M apart from an aligned base, so whole words when M is a multiple of four)
   __device__ __forceinline__ float sum_row(const SearchArgs &a, const uint8_t *__restrict__ c) const {
     float dist = 0.0f;
-    const uint32_t K = a.pq_K;
+    const uint32_t K = row_stride(a);
     if ((a.pq_M & 3u) == 0) {
       const uint32_t *__restrict__ w = reinterpret_cast<const uint32_t *>(c);
       for (uint32_t i = 0; i < a.pq_M; i += 4) {
@@ -1214,7 +1267,7 @@ struct PQDist {
   // the visited-set test, whose first LDS round trip then covers theirs, and summed after it (k_greedy_search_pq2)
   __device__ __forceinline__ bool ahead8(const SearchArgs &a) const { return a.pq_M == 8 && pre_ready; }
   __device__ __forceinline__ void load8(const SearchArgs &a, bool valid, float (&t)[8]) const {
-    const uint32_t K = a.pq_K;
+    const uint32_t K = row_stride(a);
     const uint32_t x = valid ? pre.x : 0u, y = valid ? pre.y : 0u;
     t[0] = lut[0 * K + (x & 0xFF)], t[1] = lut[1 * K + ((x >> 8) & 0xFF)];
     t[2] = lut[2 * K + ((x >> 16) & 0xFF)], t[3] = lut[3 * K + (x >> 24)];
@@ -1235,12 +1288,12 @@ struct PQDist {
     row_codes = nullptr, pre_ready = false;  // one chunk's worth (the seeds of a filtered search call hop without begin_row)
     if (!((pend >> lane) & 1ull)) return 0.0f;
     if (a.pq_M != 8) {
-      if (ready && a.pq_M == 16) return sum16(0.0f, prew[0], 0, a.pq_K);
-      if (ready && a.pq_M == 32) return sum16(sum16(0.0f, prew[0], 0, a.pq_K), prew[1], 16, a.pq_K);
+      if (ready && a.pq_M == 16) return sum16(0.0f, prew[0], 0, row_stride(a));
+      if (ready && a.pq_M == 32) return sum16(sum16(0.0f, prew[0], 0, row_stride(a)), prew[1], 16, row_stride(a));
       return rc ? sum_row(a, rc) : sum(a, nb);
     }
     float dist = 0.0f;  // same sequential adds in index order (product.go:271-275)
-    const uint32_t K = a.pq_K;
+    const uint32_t K = row_stride(a);
     dist += lut[0 * K + (pre.x & 0xFF)];
     dist += lut[1 * K + ((pre.x >> 8) & 0xFF)];
     dist += lut[2 * K + ((pre.x >> 16) & 0xFF)];
@@ -1252,6 +1305,9 @@ struct PQDist {
     return dist;
   }
 };
+typedef PQDistT<true> PQDist;               // (k_greedy_search_pq2, which keeps its table in LDS always)
+typedef PQDistT<true, true> PQLdsDist;      // the one-wave walk, table copied into LDS
+typedef PQDistT<false> PQGlobalDist;        // the one-wave walk, table where k_pq_lut left it
 
 // Binary quantizer with a threshold: dist = bitDistFn(encode(query), code[slot]) (binary.go:191-200), hammingDistance
 // or jaccardDistance of distance.go:45-67 -- integer population counts, one conversion (hamming) or one float32
@@ -1265,10 +1321,11 @@ struct BitDist {
   static constexpr bool kHasStamps = false;
   static constexpr bool kPointDistances = false;  // (the build's distance table is a full-precision store's)
   static constexpr size_t kLdsBytes = 64 * sizeof(uint64_t) + 8;  // W <= 64 query words, on an 8-byte boundary
-  const uint64_t *xq;  // LDS [W]
+  typedef __attribute__((address_space(3))) uint64_t lds_word;
+  const lds_word *xq;  // LDS [W] (typed as LDS: a generic pointer's reads and writes would be flat instructions)
   uint32_t W;
   __device__ __forceinline__ void init(const SearchArgs &a, uint32_t q, int lane, float *lds) {
-    uint64_t *w = reinterpret_cast<uint64_t *>((reinterpret_cast<uintptr_t>(lds) + 7) & ~(uintptr_t)7);
+    lds_word *w = (lds_word *)(((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)lds + 7u) & ~7u);
     const float *v = a.queries + (size_t)q * a.dim;
     W = a.bq_W;
     for (uint32_t k = 0; k < W; k++) {
@@ -1544,7 +1601,7 @@ struct PQWideDist {
       }
       const uint32_t named = sh->named;
       uint32_t nb;
-      if (mode == 1u) nb = reinterpret_cast<const uint32_t *>(sh->rowp)[lane];
+      if (mode == 1u) nb = as_global(reinterpret_cast<const uint32_t *>(sh->rowp))[lane];  // (an adjacency row: device memory)
       else nb = lane == 0 ? sh->slot : kNoSlot;
       load_codes(a, nb);
       float val[MS];
@@ -2103,6 +2160,7 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
   const int cap = (int)a.search_size;
   uint32_t n_dist = 0, n_hop = 0, n_edges = 0;
   constexpr bool kStaged = Dist::kStage != Stage::kNone;  // the two-precision hop
+  uint32_t n_sk_bad = 0;  // two-precision hop, audited: discards the exact distance contradicts
   uint32_t n_sk_out = 0;  // ... its neighbours discarded on their first-stage distance
   __shared__ uint32_t s_scatter[2 * NREG * 64];  // add_with_limit_merge scratch
 
@@ -2273,6 +2331,10 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
       SDB_STAMP(st_adj)
       if constexpr (kStaged) dist.stage_begin(a, nb, valid, len == cap);
       else dist.prefetch(a, nb, valid);
+      // (the audit flag: a scalar load issued with the copy rows and back long before the visited-set test is through --
+      // read behind the stage's sums it was a memory round trip of its own on a wave with nobody to cover it)
+      uint32_t audit = 0;
+      if constexpr (kStaged) audit = cold_args(a).sk_audit;
       // CheckAndVisit distset.go:174 -- marks before any distance test
       bool isnew;
       if (Dist::kSpeculate && have_marks && first_chunk) isnew = (mark_mask >> lane) & 1ull;
@@ -2292,11 +2354,11 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
             const float tail_d = FILT ? list_tail_bound(cd, cap, __popcll(pend), lane) : list_tail(cd, cap);
             uint64_t out = 0;
             const uint64_t keep = dist.stage_keep(a, nb, pend, lane, tail_d, out);
-            if (cold_args(a).sk_audit) {  // (rare path: counted at once, not carried in a register through the walk)
+            if (audit) {  // (rare path; the count goes out with the discarded count in the epilogue: the counters' address
+                          // read here, a scalar load inside the hop, left the filtered euclidean walk at d = 384 with a dead
+                          // 32-byte stack slot, i.e. a private segment)
               const float dx = dist.hop(a, nb, pend, lane);
-              const uint64_t bad = __ballot(((out >> lane) & 1ull) && !(dx > tail_d));
-              unsigned long long *cnt = cold_args(a).sk_counters;
-              if (bad && lane == 0 && cnt) atomicAdd(cnt + 1, (unsigned long long)__popcll(bad));
+              n_sk_bad += (uint32_t)__popcll(__ballot(((out >> lane) & 1ull) && !(dx > tail_d)));
             }
             n_sk_out += (uint32_t)__popcll(out);
             pend = keep;
@@ -2403,14 +2465,14 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
   // ---- IndexVamana.Search result copy vamana.go:293-307 (from resultSet when filtered, search.go:36)
   // (what only this epilogue reads -- outputs, trace, counters -- comes through cold_args(): loaded here, once, instead
   // of being carried, spilled into VGPR lanes, from the kernel's first instruction through the whole walk)
-  const SearchArgs &e = cold_args(a);
+  ColdArgs &e = cold_args(a);
   if (e.out_ids) {
     int base = 0;
     const int olen = FILT ? rlen : len;
     const int limit = (int)e.limit;
-    uint64_t *const o_ids = e.out_ids + (size_t)q * limit;
-    float *const o_d = e.out_dists + (size_t)q * limit;
-    const uint64_t *const ids = e.ids;
+    auto *const o_ids = as_global(e.out_ids) + (size_t)q * limit;
+    auto *const o_d = as_global(e.out_dists) + (size_t)q * limit;
+    const auto *const ids = as_global(e.ids);
 #pragma unroll
     for (int r = 0; r < NREG; r++) {
       const uint32_t s = (FILT ? rid[FILT ? r : 0] : cid[r]) & ~kVisBit;
@@ -2425,21 +2487,24 @@ __device__ __forceinline__ void search_body(const SearchArgs &a, const uint32_t 
       base += __popcll(m);
     }
     const int got = base < limit ? base : limit;
-    if (lane == 0) e.out_counts[q] = (uint32_t)got;
+    if (lane == 0) as_global(e.out_counts)[q] = (uint32_t)got;
     for (int i = got + lane; i < limit; i += 64)  // rows shorter than `limit` end in zeros, not in
       o_ids[i] = 0, o_d[i] = 0.0f;                // whatever was there
   }
   if (lane == 0) {
-    if (e.tr_ndist) e.tr_ndist[q] = n_dist;
-    if (e.tr_nhop) e.tr_nhop[q] = n_hop;
+    if (e.tr_ndist) as_global(e.tr_ndist)[q] = n_dist;
+    if (e.tr_nhop) as_global(e.tr_nhop)[q] = n_hop;
 #ifdef SDB_SPEC_STATS
-    if (e.tr_nedges) e.tr_nedges[q] = Dist::kSpeculate ? n_spec_hit : n_edges;
+    if (e.tr_nedges) as_global(e.tr_nedges)[q] = Dist::kSpeculate ? n_spec_hit : n_edges;
 #else
-    if (e.tr_nedges) e.tr_nedges[q] = n_edges;
+    if (e.tr_nedges) as_global(e.tr_nedges)[q] = n_edges;
 #endif
-    if (e.vis_count) e.vis_count[q] = n_hop;
+    if (e.vis_count) as_global(e.vis_count)[q] = n_hop;
     if constexpr (kStaged)
-      if (e.sk_counters && n_sk_out) atomicAdd(e.sk_counters, (unsigned long long)n_sk_out);
+      if (e.sk_counters && n_sk_out) {
+        atomicAdd(e.sk_counters, (unsigned long long)n_sk_out);
+        if (n_sk_bad) atomicAdd(e.sk_counters + 1, (unsigned long long)n_sk_bad);  // (only a discarded neighbour can be contradicted)
+      }
     if (e.totals) {  // one of 64 copies of the counters (index.h kStatCopies)
       unsigned long long *t = e.totals + (q & 63u) * 16u;
       atomicAdd(t, (unsigned long long)n_dist), atomicAdd(t + 1, (unsigned long long)n_edges);
@@ -2839,7 +2904,7 @@ __global__ __launch_bounds__(128) void k_greedy_search_pq2(const SearchArgs a) {
     return pq2_merger(a, q, lane, sh, s_scatter2);
   }
   PQDist dist;
-  dist.lut = lut;
+  dist.table_in_lds(lut);
   if constexpr (HCAP == kHash16) {
     HashVisited16 hv;
     hv.init_nosync(reinterpret_cast<uint32_t *>(lds_f), bits, a.words_per_query, lane, a.hash_limit, a.hash16_probes);

@@ -8,6 +8,8 @@ objects' own metadata notes (.vgpr_count, .agpr_count, .sgpr_count, .vgpr_spill_
     python3 tools/kernel_table.py --json out.json       # machine-readable
     python3 tools/kernel_table.py --check               # exit 1 if ANY kernel has scratch or spilled VGPRs, or a kernel
                                                         # spills more SGPRs than its class allows (tests use this)
+    python3 tools/kernel_table.py --memory-ops          # the walk kernels' memory instructions by kind, from the
+                                                        # disassembly, and the staged hop's load schedule (stage_span)
 
 Needs only the ROCm LLVM tools (llvm-objdump --offloading, llvm-readelf; binutils c++filt); no GPU."""
 import argparse
@@ -81,18 +83,108 @@ def kernels(so=SO):
                     cur = None
             if cur and ".name" in cur:
                 out.append(cur)
-    names = "\n".join(k[".name"] for k in out)
-    dem = subprocess.run(["c++filt"], input=names, capture_output=True, text=True, check=True).stdout.splitlines()
     rows = []
-    for k, d in zip(out, dem):
-        d = re.sub(r"\s*\[clone .*\]$", "", d)
-        d = re.sub(r"^void ", "", d)
-        d = re.sub(r"\([^()]*\)$", "", d)  # drop the parameter list (a template argument may hold parentheses of its own)
+    for k, d in zip(out, demangled([k[".name"] for k in out])):  # (without the parameter list: a template argument may hold parentheses of its own)
         row = {"kernel": d}
         for f in FIELDS:
             row[f[1:]] = int(k.get(f, "0"))
         rows.append(row)
     rows.sort(key=lambda r: r["kernel"])
+    return rows
+
+
+def demangled(names):
+    dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
+    out = []
+    for d in dem:
+        d = re.sub(r"\s*\[clone .*\]$", "", d)
+        d = re.sub(r"^void ", "", d)
+        out.append(re.sub(r"\([^()]*\)$", "", d))
+    return out
+
+
+def disassembly(so=SO, match=r"^sdb::k_greedy_search"):
+    """{demangled kernel name: [(mnemonic, operands), ...] in program order} of the kernels whose name matches"""
+    pat = re.compile(match)
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in code_objects(so, tmp):
+            text = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
+                                  capture_output=True, text=True).stdout
+            syms, cur = [], None
+            for line in text.splitlines():
+                m = re.match(r"^[0-9a-f]+ <([^>]+)>:$", line)
+                if m:
+                    cur = []
+                    syms.append((m.group(1), cur))
+                    continue
+                m = re.match(r"^\s+([a-z_][a-z0-9_]*)\s*(.*?)\s*(?://.*)?$", line)
+                if m and cur is not None:
+                    cur.append((m.group(1), m.group(2)))
+            for name, (_, ins) in zip(demangled([n for n, _ in syms]), syms):
+                if pat.match(name) and ins:
+                    out[name] = ins
+    return out
+
+
+# the staged one-wave kernels whose hop asks for the copy rows of all 64 edges ahead (search_kernel.h stage_ahead)
+AHEAD = re.compile(r"^sdb::k_greedy_search<sdb::(Int8Dist<(1|2|3)>|PlainDist<(1|2|3), (false|true), true, 4, \(sdb::Stage\)1>), ")
+
+
+def is_vmem_load(mn):
+    return mn.startswith(("global_load", "flat_load", "buffer_load"))
+
+
+def copy_row_loads(name):
+    """vector loads a hop of that kernel issues for its copy rows: 32 pairs of rows, one load per int8 row, NG per
+    float16 row, and the euclidean walk's ||y16||^2 of the lane's edge"""
+    m = AHEAD.match(name)
+    if m.group(2):
+        return 32
+    return 32 * int(m.group(3)) + (1 if m.group(4) == "true" else 0)
+
+
+def stage_span(ins, want=32):
+    """The hop's run of copy-row loads and what lies between it and the visited-set test.  Candidates are the stretches
+    of straight-line code (no branch inside) that hold at least `want` vector-memory loads; the hop's is the one whose
+    last load lies nearest in front of a ds_cmpst_rtn_b32 -- the test follows the hop's loads at once, whatever else of
+    the kernel (a prologue, a round of float32 rows) may load as many values.  The run is the last `want` loads of that
+    stretch: it may begin with the load of the adjacency row, which the copy rows' addresses wait for and which is not
+    part of the run.  Returns None when there is no such stretch with a ds_cmpst_rtn_b32 behind it, else a dict: first /
+    last (index of the run's first and last load), cmpst (index of the first ds_cmpst_rtn_b32 behind the run), loads
+    (vector loads in the stretch), vm_waits (the s_waitcnt with a vmcnt field from the run's first load to that
+    ds_cmpst_rtn_b32), other_vmem (vector-memory instructions behind the run and before the ds_cmpst_rtn_b32)."""
+    cmpsts = [j for j, (mn, _) in enumerate(ins) if mn == "ds_cmpst_rtn_b32"]
+    start, best = 0, None
+    for i, (mn, _) in enumerate(list(ins) + [("s_endpgm", "")]):
+        if mn.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")):
+            idx = [j for j in range(start, min(i, len(ins))) if is_vmem_load(ins[j][0])]
+            if len(idx) >= want:
+                nxt = next((c for c in cmpsts if c > idx[-1]), None)
+                if nxt is not None and (best is None or nxt - idx[-1] < best[2] - best[1]):
+                    best = (idx[-want], idx[-1], nxt, len(idx))
+            start = i + 1
+    if best is None:
+        return None
+    first, last, cmpst, n_loads = best
+    vm = ("global_", "flat_", "buffer_", "scratch_")
+    return {"first": first, "last": last, "cmpst": cmpst, "loads": n_loads,
+            "vm_waits": [(j, ins[j][1]) for j in range(first, cmpst) if ins[j][0] == "s_waitcnt" and "vmcnt" in ins[j][1]],
+            "other_vmem": [(j, ins[j][0]) for j in range(last + 1, cmpst) if ins[j][0].startswith(vm)]}
+
+
+def memory_ops(so=SO):
+    """rows of the --memory-ops report: per walk kernel the count of instructions by kind, and stage_span's findings"""
+    rows = []
+    for name, ins in sorted(disassembly(so).items()):
+        row = {"kernel": name}
+        for kind in ("flat_", "global_load", "global_store", "global_atomic", "s_load", "ds_"):
+            row[kind] = sum(1 for mn, _ in ins if mn.startswith(kind))
+        if AHEAD.match(name):
+            sp = stage_span(ins, copy_row_loads(name))
+            row["stage"] = None if sp is None else {"loads": sp["loads"], "vm_waits": [w for _, w in sp["vm_waits"]],
+                                                    "instructions_to_cmpst": sp["cmpst"] - sp["first"]}
+        rows.append(row)
     return rows
 
 
@@ -159,7 +251,22 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--design", action="store_true", help="the block DESIGN.md carries between its kernel_table markers")
+    ap.add_argument("--memory-ops", action="store_true", help="the walk kernels' memory instructions and the staged hop's load schedule")
     a = ap.parse_args()
+    if a.memory_ops:
+        rows = memory_ops(a.so)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        print("| kernel | flat | global load | global store | global atomic | s_load | LDS | copy-row loads in the hop's run | vmcnt waits before the visited-set test |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            st = r.get("stage", "")
+            print("| `%s` | %d | %d | %d | %d | %d | %d | %s | %s |" % (
+                r["kernel"], r["flat_"], r["global_load"], r["global_store"], r["global_atomic"], r["s_load"], r["ds_"],
+                "" if st == "" else ("not found" if st is None else st["loads"]),
+                "" if not st else (", ".join(st["vm_waits"]) or "none")))
+        return 0
     rows = kernels(a.so)
     if a.design:
         print(design_block(rows))
