@@ -64,7 +64,7 @@ def _check_walks(ix, o, thr, d, q, limit, ss, filters=None, bitmap=False):
     f = filters
     if filters is not None and bitmap:
         f = vamana.FilterBitmaps.from_sets(filters)
-    g_ids, g_d, g_c, tr = ix.search_batch(q, limit, ss, filters=f, trace=True, visit_cap=1024)
+    g_ids, g_d, g_c, tr = ix.search_batch(q, limit, ss, filters=f, trace=True, visit_cap=2048)  # (searchSize 512: 512+ hops)
     qx = bm.expand(bm.encode(q, thr), d)
     for k in range(q.shape[0]):
         o_ids, o_d, o_vis, o_tr = o.search(qx[k], limit, ss, filter_ids=None if filters is None else filters[k])
@@ -76,7 +76,10 @@ def _check_walks(ix, o, thr, d, q, limit, ss, filters=None, bitmap=False):
         assert np.array_equal(tr.visit_ids[k, :o_tr.n_hop], o_vis), (k, limit, ss)
 
 
-CASES = [(1, 1), (10, 10), (10, 64), (10, 65), (10, 75), (100, 100), (10, 128), (10, 129)]
+# (searchSize 129 .. 512: the eight-register candidate array, k_greedy_search<BitDist, 8, *, 0>; limit > 64: a result row
+# that crosses its registers -- and nearly every bit distance ties with others)
+LARGE_CASES = [(10, 256), (129, 129), (512, 512)]
+CASES = [(1, 1), (10, 10), (10, 64), (10, 65), (10, 75), (100, 100), (10, 128), (10, 129)] + LARGE_CASES
 
 
 # ---- 1. the quantizer object ----------------------------------------------------------------------------------
@@ -462,6 +465,17 @@ def test_filtered_hamming_search(cosine_table, ragged_table, kind, bitmap):
             _check_walks(t.ix, t.o, t.thr, t.d, t.q[:16], limit, ss, filters=f, bitmap=bitmap)
 
 
+def test_filtered_hamming_search_at_the_largest_array(cosine_table):
+    """(512, 65): eight array registers and a result row of two, seeded by 170 ids, by half the table, by unknown ids;
+    as id lists and as bitmaps"""
+    t = cosine_table
+    ids = t.ix.export(with_vectors=False)[0]
+    for kind in ("few", "half", "unknown"):
+        f = _filters(np.random.default_rng(512 + 65), ids, 16, kind, 512)
+        for bitmap in (False, True):
+            _check_walks(t.ix, t.o, t.thr, t.d, t.q[:16], 65, 512, filters=f, bitmap=bitmap)
+
+
 @pytest.mark.parametrize("bitmap", [False, True])
 def test_filtered_search_after_deletes(oracle, bitmap):
     """a table with deleted rows: filter ids go through the device's id -> slot table"""
@@ -537,6 +551,9 @@ def test_jaccard_search_equals_the_restatement():
             f = _filters(rng, ids, 32, kind, ss)
             _check_walks_model(ix, g, thr, q, limit, ss, filters=f)
             _check_walks_model(ix, g, thr, q, limit, ss, filters=f, bitmap=True)
+    for limit, ss in LARGE_CASES:  # (500 rows: at 512 the array never fills)
+        _check_walks_model(ix, g, thr, q[:12], limit, ss)
+    _check_walks_model(ix, g, thr, q[:12], 129, 129, filters=_filters(rng, ids, 12, "half", 129))
     ix.set_tuning("no_hash", 1)
     _check_walks_model(ix, g, thr, q, 10, 75)
     # the exact scan and explicit distances under jaccard
