@@ -222,6 +222,37 @@ int sdb_index_search_batch_bitmap(sdb_index *ix, uint64_t nq, const float *queri
                                   const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
                                   const sdb_search_trace *trace, int mem, void *stream);
 
+/* Re-ranked search: the library's own extension -- the reference returns a quantized store's order and the quantizer's
+ * distances, and so do the two calls above, which this one leaves as they are.  It is a call of its own, not a tuning
+ * knob (no knob changes a result; this changes the answer).  Both quantizers keep the float32 rows in HBM; for one query:
+ *   1. (cid[j], cn) = what sdb_index_search_batch returns for limit = rerank, the same search_size and filter, on the
+ *      same committed view: the walk's candidates in the walk's order, start node removed;
+ *   2. e[j] = the index's float32 distance function (sdb_index_params.metric) between the query and the stored float32
+ *      row of cid[j] -- the reference's chains and reduce tree, bit for bit what sdb_index_distance_batch returns on an
+ *      index without a quantizer (an id the store does not know: math.MaxFloat32; the walk returns none);
+ *   3. the candidates are put in the order of (isnan(e[j]), e[j], j): IEEE compares (-0.0 and 0.0 tie), ties keep the
+ *      walk's order, NaNs come last in the walk's order;
+ *   4. the first min(limit, cn) of them are written: out_ids their ids, out_dists THE EXACT DISTANCES e (not the
+ *      quantizer's), out_counts = min(limit, cn); the unused entries are 0 / 0.0f as the walks leave them.
+ * limit <= rerank <= search_size, otherwise SDB_ERR_INVALID with nothing written; every other argument and check as in
+ * sdb_index_search_batch / _bitmap (strict mode, searchSize 1 .. 512, `mem`, `stream`).  The trace is the walk's, untouched:
+ * the exact evaluations are NOT counted in n_dist.  Any index: product quantizer, binary quantizer (hamming / jaccard),
+ * or none -- there the answer is sdb_index_search_batch(limit)'s whenever the distances are finite (the array is in
+ * exact order already and both orders keep the array's among ties).  What it reads beyond the walk: rerank float32 rows
+ * per query, by one more kernel on the same stream and the same view.  On a table whose ids are not consecutive
+ * (deletes, arbitrary ids) the candidates are resolved through the view's id -> slot table, and the call returns once its
+ * kernels have run, in device memory too.  With sdb_index_set_profiling such a call records two durations: the walk's,
+ * then the re-rank kernel's. */
+int sdb_index_search_batch_rerank(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
+                                  uint32_t rerank, const uint64_t *filter_offsets, const uint64_t *filter_ids,
+                                  uint64_t *out_ids, float *out_dists, uint32_t *out_counts, const sdb_search_trace *trace,
+                                  int mem, void *stream);
+int sdb_index_search_batch_bitmap_rerank(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit,
+                                         uint32_t search_size, uint32_t rerank, const uint64_t *filter_first_id,
+                                         const uint64_t *filter_word_offsets, const uint64_t *filter_words,
+                                         uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
+                                         const sdb_search_trace *trace, int mem, void *stream);
+
 /* plainStore.DistanceFromFloat (shard/vectorstore/plain.go:76-85) batched: distances from each
  * query to an explicit list of stored node ids (nc per query, cand_ids[nq*nc], host memory).
  * Unknown ids give math.MaxFloat32, as the reference does for a foreign point type

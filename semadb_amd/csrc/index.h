@@ -29,6 +29,8 @@ struct Workspace {
   size_t filter_aux_bytes = 0;
   void *filter_host = nullptr;  // the same lists as the host threads write them: pinned, so that the upload is one DMA
   size_t filter_host_bytes = 0;
+  void *rerank = nullptr;  // a re-ranked batch's walk results: [nq][rerank] ids, [nq][rerank] distances, [nq] counts (rerank.hip)
+  size_t rerank_bytes = 0;
   hipEvent_t launched = nullptr;   // recorded behind the last search kernels that were given a graph version
   bool launched_valid = false;
   // a device-memory search returns right behind its kernels: `launched` then also marks the end of the call's device
@@ -42,6 +44,7 @@ struct Workspace {
   int ensure_filter(size_t bytes);
   int ensure_filter_host(size_t bytes);
   int ensure_filter_aux(size_t bytes);
+  int ensure_rerank(size_t bytes);
   int ensure_lut(size_t bytes);
   int ensure_bitsets(size_t bytes);
   int ensure_scratch(size_t bytes);
@@ -49,6 +52,33 @@ struct Workspace {
 };
 
 struct PQState;  // pq.hip
+
+// Re-ranking of a walk's candidates by their stored float32 rows (rerank.hip k_rerank; semadb_amd.h
+// sdb_index_search_batch_rerank).  cand_*: what the walk wrote with limit = rerank; out_*: where the call's answer goes.
+struct RerankArgs {
+  const float *slab = nullptr, *queries = nullptr;
+  const uint64_t *cand_ids = nullptr;   // [nq][rerank], walk order
+  const uint32_t *cand_cnt = nullptr;   // [nq]
+  uint64_t *out_ids = nullptr;          // [nq][limit]
+  float *out_dists = nullptr;           // [nq][limit]
+  uint32_t *out_counts = nullptr;       // [nq]
+  // id -> slot on the committed view: keys == NULL: id - base_id (consecutive ids); else a probe of sdb_index::IdMap
+  const uint64_t *keys = nullptr;
+  const uint32_t *vals = nullptr;
+  uint32_t mask = 0;
+  uint64_t base_id = 0;
+  uint32_t view_n = 0;
+  uint32_t dim = 0, nblk = 0, ng = 0, tail = 0, ld = 0;
+  uint32_t rerank = 0, limit = 0;
+  int metric = 0;
+};
+constexpr uint32_t kRerankMax = 512;  // searchSize's ceiling on the device (launch_greedy_search)
+int launch_rerank(const RerankArgs &a, uint32_t nq, hipStream_t stream);
+
+#ifdef __HIPCC__
+// the hash of sdb_index::IdMap (k_idmap_build fills the table; k_filter_resolve and k_rerank probe it)
+__device__ __forceinline__ uint32_t idmap_hash(uint64_t id) { return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32); }
+#endif
 
 // (sdb::ViewMutex, the writer-preferring lock around an index's committed view: view_mutex.h -- HIP-free, stress-tested
 // under ThreadSanitizer by tests/host/test_concurrency.cpp)

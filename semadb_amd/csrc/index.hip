@@ -80,6 +80,15 @@ int Workspace::ensure_filter_aux(size_t bytes) {
   return SDB_OK;
 }
 
+int Workspace::ensure_rerank(size_t bytes) {
+  if (bytes <= rerank_bytes) return SDB_OK;
+  if (rerank) SDB_HIP(hipFree(rerank));
+  rerank = nullptr, rerank_bytes = 0;
+  SDB_HIP(hipMalloc(&rerank, bytes));
+  rerank_bytes = bytes;
+  return SDB_OK;
+}
+
 int Workspace::ensure_filter_host(size_t bytes) {
   if (bytes <= filter_host_bytes) return SDB_OK;
   if (filter_host) SDB_HIP(hipHostFree(filter_host));
@@ -108,6 +117,8 @@ void Workspace::release() {
   filter_aux = nullptr, filter_aux_bytes = 0;
   if (lut) (void)hipFree(lut);
   lut = nullptr;
+  if (rerank) (void)hipFree(rerank);
+  rerank = nullptr, rerank_bytes = 0;
   if (bitsets) (void)hipFree(bitsets);
   if (scratch) (void)hipFree(scratch);
   if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -202,7 +213,6 @@ __global__ __launch_bounds__(64) void k_compact_rows(const uint32_t *__restrict_
 // and a query for which they are not raises flags[2]: the walk then answers Contains from the ids themselves
 // (SearchArgs::filt_ids); the seeds are the first slots in id order either way.
 // flags[0]: != 0 when some query's ids are not strictly ascending; flags[1]: one such query.
-__device__ __forceinline__ uint32_t idmap_hash(uint64_t id) { return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32); }
 __global__ void k_idmap_build(const uint64_t *__restrict__ ids, uint32_t n, uint64_t *__restrict__ keys,
                               uint32_t *__restrict__ vals, uint32_t mask) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1799,13 +1809,20 @@ constexpr int kBitmapNeedsIds = -7001;  // search_batch_impl: this table cannot 
 static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit,
                              uint32_t search_size, const uint64_t *filter_offsets,
                              const uint64_t *filter_ids, const BitmapFilters *bm, uint64_t *out_ids, float *out_dists,
-                             uint32_t *out_counts, const sdb_search_trace *trace, int mem, void *stream_) {
+                             uint32_t *out_counts, const sdb_search_trace *trace, int mem, void *stream_,
+                             uint32_t rerank = 0) {
+  // rerank != 0 (sdb_index_search_batch_rerank): the walk is launched exactly as without it, with limit = rerank and its
+  // three outputs in the workspace; k_rerank (rerank.hip) then writes where the walk would have written
   if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
   if (nq == 0) return SDB_OK;
   if (!queries || !out_ids || !out_dists || !out_counts) return fail(SDB_ERR_INVALID, "NULL argument");
   if (limit < 1) return fail(SDB_ERR_INVALID, "invalid limit %u for vector query", limit);
   if (search_size < limit)  // search.go:23-25
     return fail(SDB_ERR_INVALID, "searchSize (%u) must be greater than k (%u)", search_size, limit);
+  if (rerank && (rerank < limit || rerank > search_size))
+    return fail(SDB_ERR_INVALID, "rerank (%u) must lie between k (%u) and searchSize (%u)", rerank, limit, search_size);
+  if (rerank && search_size > kRerankMax)
+    return fail(SDB_ERR_INVALID, "searchSize %u not supported on device (1..512)", search_size);
   if (ix->P.strict && (search_size < 25 || search_size > 75 || limit > 75))  // models/search.go:287-297
     return fail(SDB_ERR_INVALID, "invalid searchSize %u / limit %u for vector query, expected 25-75 / 1-75",
                 search_size, limit);
@@ -1837,6 +1854,25 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
   const uint32_t words = ((vw.n + 31) / 32 + 31) & ~31u;  // per-query bitset, 128-byte multiple
   const size_t bs_bytes = (size_t)nq * words * sizeof(uint32_t);
   SDB_TRY(ws->ensure_bitsets(filtered ? 2 * bs_bytes : bs_bytes));
+  // re-ranking: the walk's candidates stay in the workspace, and their ids become slots again on the device -- by the
+  // committed view's id -> slot table where the ids are not consecutive (built here, before anything is enqueued)
+  RerankArgs ra{};
+  float *rr_dists = nullptr;
+  if (rerank) {
+    const size_t b_ids = ((size_t)nq * rerank * sizeof(uint64_t) + 255) & ~(size_t)255;
+    const size_t b_d = ((size_t)nq * rerank * sizeof(float) + 255) & ~(size_t)255;
+    SDB_TRY(ws->ensure_rerank(b_ids + b_d + nq * sizeof(uint32_t)));
+    if (!ix->dense_ids) {
+      SDB_TRY(ix->ensure_idmap(vw, stream));
+      ra.keys = ix->idmap.keys, ra.vals = ix->idmap.vals, ra.mask = ix->idmap.cells - 1;
+    }
+    char *rb = static_cast<char *>(ws->rerank);
+    ra.cand_ids = reinterpret_cast<uint64_t *>(rb), ra.cand_cnt = reinterpret_cast<uint32_t *>(rb + b_ids + b_d);
+    rr_dists = reinterpret_cast<float *>(rb + b_ids);  // (the quantizer's distances: written by the walk, read by nobody)
+    ra.base_id = ix->h_ids.empty() ? 0 : ix->h_ids[0], ra.view_n = vw.n;
+    ra.slab = ix->d_slab, ra.dim = l.dim, ra.nblk = l.nblk, ra.ng = l.ng, ra.tail = l.tail, ra.ld = l.ld;
+    ra.rerank = rerank, ra.limit = limit, ra.metric = (int)ix->P.metric;
+  }
 
   SearchArgs a{};
   a.slab = ix->d_slab, a.adj = vw.adj, a.ids = vw.ids;
@@ -2064,7 +2100,7 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
   a.dim = l.dim, a.nblk = l.nblk, a.ng = l.ng, a.tail = l.tail, a.ld = l.ld;
   a.start_slot = (uint32_t)ix->start_slot;
   a.start_ext = vw.start_ext, a.start_ext_n = vw.start_ext_n;
-  a.search_size = search_size, a.limit = limit, a.metric = (int)ix->P.metric;
+  a.search_size = search_size, a.limit = rerank ? rerank : limit, a.metric = (int)ix->P.metric;
   a.hash_limit = ix->tune_hash_limit, a.prefer_bitset = ix->tune_no_hash ? 1u : 0u;
   a.wide_hash = ix->tune_wide_hash ? 1u : 0u, a.hash16_probes = ix->tune_hash16_probes;
   a.pq_narrow = ix->tune_pq_narrow;
@@ -2100,6 +2136,10 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
     // ClearAll (distset.go:101); the LDS hash variant clears a bitset only for a query that overflows it
     if (!search_uses_hash(a, (uint32_t)nq) && !sketch_walk(a, (uint32_t)nq))
       SDB_HIP(hipMemsetAsync(ws->bitsets, 0, filtered ? 2 * bs_bytes : bs_bytes, stream));
+    if (rerank) {  // the walk's outputs go to the workspace; what the caller (or the staging below) named is k_rerank's to write
+      ra.queries = a.queries, ra.out_ids = a.out_ids, ra.out_dists = a.out_dists, ra.out_counts = a.out_counts;
+      a.out_ids = const_cast<uint64_t *>(ra.cand_ids), a.out_dists = rr_dists, a.out_counts = const_cast<uint32_t *>(ra.cand_cnt);
+    }
     const bool prof = ix->profiling && !ix->ev0.empty();
     const uint32_t slot = (uint32_t)(ix->prof_count % sdb_index::kProfRing);
     if (prof) (void)hipEventRecord(ix->ev0[slot], stream);
@@ -2107,6 +2147,22 @@ static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, u
     if (prof) {
       (void)hipEventRecord(ix->ev1[slot], stream);
       ix->prof_count++;
+    }
+    if (rerank) a.out_ids = ra.out_ids, a.out_dists = ra.out_dists, a.out_counts = ra.out_counts;  // (the copies below read these)
+    if (rerank && rc == SDB_OK) {  // same stream, same view, still under the shared lock: no commit comes between the two
+      const uint32_t slot2 = (uint32_t)(ix->prof_count % sdb_index::kProfRing);  // a profiled call records two entries: walk, re-rank
+      if (prof) (void)hipEventRecord(ix->ev0[slot2], stream);
+      rc = launch_rerank(ra, (uint32_t)nq, stream);
+      if (prof) {
+        (void)hipEventRecord(ix->ev1[slot2], stream);
+        ix->prof_count++;
+      }
+      // the id -> slot table is this view's only while the shared lock is held (sdb_index::IdMap: the next view's first
+      // filtered or re-ranked search rebuilds it in place): like k_filter_resolve, the probe has run before the lock goes
+      if (ra.keys && rc == SDB_OK && hipStreamSynchronize(stream) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(SDB_ERR_DEVICE, "re-ranked search failed on the device");
+      }
     }
     // from here on a commit may hand the copy this batch walks to the writer: it waits for this event first
     if (!ws->launched) (void)hipEventCreateWithFlags(&ws->launched, hipEventDisableTiming);
@@ -2201,15 +2257,16 @@ int sdb_index_search_batch(sdb_index *ix, uint64_t nq, const float *queries, uin
 }
 SDB_API_CATCH("sdb_index_search_batch")
 
-int sdb_index_search_batch_bitmap(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
-                                  const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
-                                  const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
-                                  const sdb_search_trace *trace, int mem, void *stream_) try {
+// sdb_index_search_batch_bitmap and its re-ranked form (rerank != 0)
+static int search_batch_bitmap_impl(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
+                                    const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
+                                    const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
+                                    const sdb_search_trace *trace, int mem, void *stream_, uint32_t rerank) {
   if (!filter_first_id || !filter_word_offsets) return fail(SDB_ERR_INVALID, "NULL filter argument");
   if (nq && filter_word_offsets[nq] > filter_word_offsets[0] && !filter_words) return fail(SDB_ERR_INVALID, "filter_words is NULL");
   const BitmapFilters bm{filter_first_id, filter_word_offsets, filter_words};
   const int rc = search_batch_impl(ix, nq, queries, limit, search_size, nullptr, nullptr, &bm, out_ids, out_dists, out_counts, trace,
-                                   mem, stream_);
+                                   mem, stream_, rerank);
   if (rc != kBitmapNeedsIds) return rc;
   // a table whose ids are not consecutive (deletes, arbitrary ids): the host's hash map resolves ids, so the bitmaps
   // become id lists here -- the reference iterates its roaring bitmap the same way (search.go:41-48)
@@ -2223,9 +2280,38 @@ int sdb_index_search_batch_bitmap(sdb_index *ix, uint64_t nq, const float *queri
   }
   if (ids.empty()) ids.push_back(0);
   return search_batch_impl(ix, nq, queries, limit, search_size, off.data(), ids.data(), nullptr, out_ids, out_dists, out_counts, trace,
-                           mem, stream_);
+                           mem, stream_, rerank);
+}
+
+int sdb_index_search_batch_bitmap(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
+                                  const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
+                                  const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
+                                  const sdb_search_trace *trace, int mem, void *stream_) try {
+  return search_batch_bitmap_impl(ix, nq, queries, limit, search_size, filter_first_id, filter_word_offsets, filter_words, out_ids,
+                                  out_dists, out_counts, trace, mem, stream_, 0);
 }
 SDB_API_CATCH("sdb_index_search_batch_bitmap")
+
+// The library's own extension (the reference does not re-rank): the walk's first `rerank` candidates in the order of
+// their stored float32 rows' distances (semadb_amd.h; rerank.hip).  rerank = 0 is no re-ranked search.
+int sdb_index_search_batch_rerank(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
+                                  uint32_t rerank, const uint64_t *filter_offsets, const uint64_t *filter_ids, uint64_t *out_ids,
+                                  float *out_dists, uint32_t *out_counts, const sdb_search_trace *trace, int mem, void *stream_) try {
+  if (rerank == 0) return fail(SDB_ERR_INVALID, "rerank (0) must lie between k (%u) and searchSize (%u)", limit, search_size);
+  return search_batch_impl(ix, nq, queries, limit, search_size, filter_offsets, filter_ids, nullptr, out_ids, out_dists, out_counts,
+                           trace, mem, stream_, rerank);
+}
+SDB_API_CATCH("sdb_index_search_batch_rerank")
+
+int sdb_index_search_batch_bitmap_rerank(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
+                                         uint32_t rerank, const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
+                                         const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
+                                         const sdb_search_trace *trace, int mem, void *stream_) try {
+  if (rerank == 0) return fail(SDB_ERR_INVALID, "rerank (0) must lie between k (%u) and searchSize (%u)", limit, search_size);
+  return search_batch_bitmap_impl(ix, nq, queries, limit, search_size, filter_first_id, filter_word_offsets, filter_words, out_ids,
+                                  out_dists, out_counts, trace, mem, stream_, rerank);
+}
+SDB_API_CATCH("sdb_index_search_batch_bitmap_rerank")
 
 int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
   if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");

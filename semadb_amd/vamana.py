@@ -387,9 +387,11 @@ class IndexVamana:
             results.append(SearchResult(int(ids[0, i]), d, np.float32(-1) * d * weight))  # vamana.go:303
         return set(r.NodeId for r in results), results
 
-    def search_batch(self, queries, limit, search_size, filters=None, trace=False, visit_cap=0, out=None):
+    def search_batch(self, queries, limit, search_size, filters=None, trace=False, visit_cap=0, out=None, rerank=None):
         """nq queries at once.  numpy in -> numpy out (synchronous); torch CUDA in -> torch out, enqueued
-        on the current stream.  Returns (ids [nq,limit] uint64, dists, counts, BatchTrace|None)."""
+        on the current stream.  Returns (ids [nq,limit] uint64, dists, counts, BatchTrace|None).
+        rerank=r (limit <= r <= search_size; sdb_index_search_batch_rerank, not in the reference): the walk's first r
+        candidates ordered by the exact float32 distance of their stored rows, which is also the distance returned."""
         k, qp, mem, shape = _buf.as_f32(queries)
         if len(shape) != 2 or shape[1] != self.parameters.VectorSize:
             raise SemaDBError(1, "query vector length must be %d" % self.parameters.VectorSize)
@@ -436,6 +438,17 @@ class IndexVamana:
                 vis, visp = _buf.empty_like_mem(mem, (nq, visit_cap), "uint64", self.device, zero=True)
             tr_struct = SearchTrace(ndp, nhp, nep, visp, visit_cap)
             tr_out = BatchTrace(nd, nh, ne, vis)
+        if rerank is not None:
+            tr_p = C.byref(tr_struct) if tr_struct is not None else None
+            if bitmaps is not None:
+                check(lib().sdb_index_search_batch_bitmap_rerank(self._h, nq, qp, limit, search_size, int(rerank),
+                                                                 _buf.np_ptr(bitmaps.first_id), _buf.np_ptr(bitmaps.word_offsets),
+                                                                 _buf.np_ptr(bitmaps.words), idp, dp, cp, tr_p, mem,
+                                                                 _buf.current_stream(mem)))
+            else:
+                check(lib().sdb_index_search_batch_rerank(self._h, nq, qp, limit, search_size, int(rerank), _buf.np_ptr(f_off),
+                                                          _buf.np_ptr(f_ids), idp, dp, cp, tr_p, mem, _buf.current_stream(mem)))
+            return ids, dists, counts, tr_out
         if bitmaps is not None:
             check(lib().sdb_index_search_batch_bitmap(self._h, nq, qp, limit, search_size, _buf.np_ptr(bitmaps.first_id),
                                                       _buf.np_ptr(bitmaps.word_offsets), _buf.np_ptr(bitmaps.words), idp,
