@@ -13,24 +13,47 @@ namespace sdb {
 
 constexpr uint32_t kAdjStride = 64;  // adjacency row stride in u32 (DegreeBound <= 64, models/index.go:279)
 
+// A buffer that only grows, kept with its byte count.  ensure() frees, nulls both fields, allocates, then sets the size: a
+// failed allocation leaves {nullptr, 0}, never a pointer with a stale size.  pinned: page-locked host memory, which
+// grows in steps of a quarter (pinning is the expensive part); otherwise device memory.
+struct GrowBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  bool pinned = false;
+  int ensure(size_t want);
+  void free();
+  template <class T>
+  T *as() const { return static_cast<T *>(p); }
+};
+
+// Lays arrays out in one buffer, each at a 256-byte boundary: take<T>(count) while the sizes are being added up (`off`
+// is then what the buffer needs), Part::in(base) once the buffer is there.
+struct Carve {
+  template <class T>
+  struct Part {
+    size_t at;
+    T *in(void *base) const { return reinterpret_cast<T *>(static_cast<char *>(base) + at); }
+  };
+  size_t off = 0;
+  template <class T>
+  Part<T> take(size_t count) {
+    const Part<T> part{off};
+    off += (count * sizeof(T) + 255) & ~(size_t)255;
+    return part;
+  }
+};
+
 // Everything one in-flight batch needs besides the index itself.  One per stream.
 struct Workspace {
   int device = 0;
   hipStream_t own_stream = nullptr;  // used by host-memory calls
-  uint32_t *bitsets = nullptr;       // [nq][words]: the per-search VisitedBitSet (distset.go:89-116)
-  size_t bitset_bytes = 0;
-  void *scratch = nullptr;  // staging for host-memory calls
-  size_t scratch_bytes = 0;
-  float *lut = nullptr;  // [nq][M*K] product-quantizer distance tables of the batch
-  size_t lut_bytes = 0;
-  void *filter = nullptr;  // seeds / filter slot lists of a filtered batch
-  size_t filter_bytes = 0;
-  void *filter_aux = nullptr;  // a batch's filter bitmaps and their per-query counts (sdb_index_search_batch_bitmap)
-  size_t filter_aux_bytes = 0;
-  void *filter_host = nullptr;  // the same lists as the host threads write them: pinned, so that the upload is one DMA
-  size_t filter_host_bytes = 0;
-  void *rerank = nullptr;  // a re-ranked batch's walk results: [nq][rerank] ids, [nq][rerank] distances, [nq] counts (rerank.hip)
-  size_t rerank_bytes = 0;
+  GrowBuf bitsets;      // uint32 [nq][words]: the per-search VisitedBitSet (distset.go:89-116)
+  GrowBuf scratch;      // staging for host-memory calls
+  GrowBuf lut;          // float [nq][M*K] product-quantizer distance tables of the batch
+  GrowBuf filter;       // seeds / filter slot lists of a filtered batch
+  GrowBuf filter_aux;   // a batch's filter bitmaps and their per-query counts (sdb_index_search_batch_bitmap)
+  GrowBuf filter_host{nullptr, 0, true};  // the same lists as the host threads write them: pinned, so that the upload is one DMA
+  GrowBuf rerank;       // a re-ranked batch's walk results: [nq][rerank] ids, [nq][rerank] distances, [nq] counts (rerank.hip)
   hipEvent_t launched = nullptr;   // recorded behind the last search kernels that were given a graph version
   bool launched_valid = false;
   // a device-memory search returns right behind its kernels: `launched` then also marks the end of the call's device
@@ -41,13 +64,6 @@ struct Workspace {
   bool pending = false;            // device work of an asynchronous call may still be running
   hipStream_t bound_stream = nullptr;
   hipEvent_t done = nullptr;
-  int ensure_filter(size_t bytes);
-  int ensure_filter_host(size_t bytes);
-  int ensure_filter_aux(size_t bytes);
-  int ensure_rerank(size_t bytes);
-  int ensure_lut(size_t bytes);
-  int ensure_bitsets(size_t bytes);
-  int ensure_scratch(size_t bytes);
   void release();
 };
 
@@ -75,8 +91,14 @@ struct RerankArgs {
 constexpr uint32_t kRerankMax = 512;  // searchSize's ceiling on the device (launch_greedy_search)
 int launch_rerank(const RerankArgs &a, uint32_t nq, hipStream_t stream);
 
+// index.hip, for the search call (search_batch.hip; launch_greedy_search and search_uses_hash: search_kernel.h)
+struct SearchArgs;
+bool sketch_walk(const SearchArgs &a, uint32_t nq);  // the call takes the two-precision hop's kernel (its visited set needs no clearing ahead)
+// the device's address of page-locked host memory the kernels can read and write in place; false: pageable, or not mapped
+bool device_view_of_host(const void *p, size_t bytes, void **dev);
+
 #ifdef __HIPCC__
-// the hash of sdb_index::IdMap (k_idmap_build fills the table; k_filter_resolve and k_rerank probe it)
+// the hash of sdb_index::IdMap (index.hip k_idmap_build fills the table; search_batch.hip k_filter_resolve and k_rerank probe it)
 __device__ __forceinline__ uint32_t idmap_hash(uint64_t id) { return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32); }
 #endif
 
@@ -267,3 +289,25 @@ struct sdb_index {
   sdb::Workspace *acquire_ws(hipStream_t stream, bool async) const;
   void release_ws(sdb::Workspace *ws, hipStream_t stream, bool async) const;
 };
+
+// id -> slot on the host (inline: a filter's translation asks once per id, search_batch.hip resolve_ids_on_host)
+inline int64_t sdb_index::slot_of(uint64_t id) const {
+  if (n == 0) return -1;
+  if (dense_ids) {
+    uint64_t base = h_ids[0];
+    if (id < base || id - base >= n) return -1;
+    return (int64_t)(id - base);
+  }
+  auto it = id2slot.find(id);
+  // (an insert in progress has entered its ids at the slots they will have: rows past n are not there yet)
+  return it == id2slot.end() || it->second >= n ? -1 : (int64_t)it->second;
+}
+
+inline int64_t sdb_index::slot_of_committed(uint64_t id, uint32_t view_n) const {
+  int64_t s = slot_of(id);
+  if ((s < 0 || (uint32_t)s >= view_n) && in_tx) {  // removed or replaced by the open transaction: the committed row is still there for a search on the committed graph
+    auto it = tx_deleted.find(id);
+    if (it != tx_deleted.end()) s = (int64_t)it->second;
+  }
+  return (s >= 0 && (uint32_t)s < view_n) ? s : -1;  // rows past the committed count belong to the transaction
+}

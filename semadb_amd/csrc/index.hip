@@ -1,4 +1,5 @@
-// index.hip -- K3 (HBM slab + adjacency loader) and the host side of K2 (search_batch).
+// index.hip -- K3 (HBM slab + adjacency loader), the index's host-side state and K2's launcher (launch_greedy_search); the
+// search call itself is search_batch.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -44,89 +45,33 @@ int on_exception(const char *fn) noexcept {
 // ------------------------------------------------------------------------------------------
 // workspaces
 // ------------------------------------------------------------------------------------------
-int Workspace::ensure_bitsets(size_t bytes) {
-  if (bytes <= bitset_bytes) return SDB_OK;
-  if (bitsets) SDB_HIP(hipFree(bitsets));
-  bitsets = nullptr, bitset_bytes = 0;
-  SDB_HIP(hipMalloc(&bitsets, bytes));
-  bitset_bytes = bytes;
+int GrowBuf::ensure(size_t want) {
+  if (want <= bytes) return SDB_OK;
+  if (p) SDB_HIP(pinned ? hipHostFree(p) : hipFree(p));
+  p = nullptr, bytes = 0;
+  if (pinned) {
+    want += want / 4;
+    SDB_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+  } else {
+    SDB_HIP(hipMalloc(&p, want));
+  }
+  bytes = want;
   return SDB_OK;
 }
 
-int Workspace::ensure_scratch(size_t bytes) {
-  if (bytes <= scratch_bytes) return SDB_OK;
-  if (scratch) SDB_HIP(hipFree(scratch));
-  scratch = nullptr, scratch_bytes = 0;
-  SDB_HIP(hipMalloc(&scratch, bytes));
-  scratch_bytes = bytes;
-  return SDB_OK;
-}
-
-int Workspace::ensure_filter(size_t bytes) {
-  if (bytes <= filter_bytes) return SDB_OK;
-  if (filter) SDB_HIP(hipFree(filter));
-  filter = nullptr, filter_bytes = 0;
-  SDB_HIP(hipMalloc(&filter, bytes));
-  filter_bytes = bytes;
-  return SDB_OK;
-}
-
-int Workspace::ensure_filter_aux(size_t bytes) {
-  if (bytes <= filter_aux_bytes) return SDB_OK;
-  if (filter_aux) SDB_HIP(hipFree(filter_aux));
-  filter_aux = nullptr, filter_aux_bytes = 0;
-  SDB_HIP(hipMalloc(&filter_aux, bytes));
-  filter_aux_bytes = bytes;
-  return SDB_OK;
-}
-
-int Workspace::ensure_rerank(size_t bytes) {
-  if (bytes <= rerank_bytes) return SDB_OK;
-  if (rerank) SDB_HIP(hipFree(rerank));
-  rerank = nullptr, rerank_bytes = 0;
-  SDB_HIP(hipMalloc(&rerank, bytes));
-  rerank_bytes = bytes;
-  return SDB_OK;
-}
-
-int Workspace::ensure_filter_host(size_t bytes) {
-  if (bytes <= filter_host_bytes) return SDB_OK;
-  if (filter_host) SDB_HIP(hipHostFree(filter_host));
-  filter_host = nullptr, filter_host_bytes = 0;
-  bytes += bytes / 4;  // grows in steps: pinning is the expensive part
-  SDB_HIP(hipHostMalloc(&filter_host, bytes, hipHostMallocDefault));
-  filter_host_bytes = bytes;
-  return SDB_OK;
-}
-
-int Workspace::ensure_lut(size_t bytes) {
-  if (bytes <= lut_bytes) return SDB_OK;
-  if (lut) SDB_HIP(hipFree(lut));
-  lut = nullptr, lut_bytes = 0;
-  SDB_HIP(hipMalloc(&lut, bytes));
-  lut_bytes = bytes;
-  return SDB_OK;
+void GrowBuf::free() {
+  if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+  p = nullptr, bytes = 0;
 }
 
 void Workspace::release() {
-  if (filter) (void)hipFree(filter);
-  filter = nullptr;
-  if (filter_host) (void)hipHostFree(filter_host);
-  filter_host = nullptr, filter_host_bytes = 0;
-  if (filter_aux) (void)hipFree(filter_aux);
-  filter_aux = nullptr, filter_aux_bytes = 0;
-  if (lut) (void)hipFree(lut);
-  lut = nullptr;
-  if (rerank) (void)hipFree(rerank);
-  rerank = nullptr, rerank_bytes = 0;
-  if (bitsets) (void)hipFree(bitsets);
-  if (scratch) (void)hipFree(scratch);
+  for (GrowBuf *b : {&filter, &filter_host, &filter_aux, &lut, &rerank, &bitsets, &scratch}) b->free();
   if (own_stream) (void)hipStreamDestroy(own_stream);
+  own_stream = nullptr;
   if (done) (void)hipEventDestroy(done);
   done = nullptr;
   if (launched) (void)hipEventDestroy(launched);
   launched = nullptr, launched_valid = false;
-  bitsets = nullptr, scratch = nullptr, own_stream = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -204,15 +149,8 @@ __global__ __launch_bounds__(64) void k_compact_rows(const uint32_t *__restrict_
     for (uint32_t i = lane; i < M; i += 64) ncodes[(size_t)j * M + i] = codes[(size_t)s * M + i];
 }
 
-// The filter of a search is a set of node ids (a roaring bitmap in the reference, search.go:33-51,93); the walk wants
-// slots: per query the slots of the ids that exist, ascending (Contains, :93), and how many of the first searchSize ids
-// exist (the seeds, :41-48).  One wave per query resolves its ids in place -- the compacted slots at the start of the
-// query's own segment.  MAP = false: a table whose ids are consecutive (id = base + slot: resolving is a subtraction,
-// and ascending ids are ascending slots).  MAP = true: any other table -- a probe of the committed view's id -> slot
-// table (sdb_index::IdMap); rows are appended in the order they arrive, so ascending ids USUALLY are ascending slots,
-// and a query for which they are not raises flags[2]: the walk then answers Contains from the ids themselves
-// (SearchArgs::filt_ids); the seeds are the first slots in id order either way.
-// flags[0]: != 0 when some query's ids are not strictly ascending; flags[1]: one such query.
+// fills the committed view's id -> slot table (sdb_index::IdMap; ensure_idmap), which search_batch.hip k_filter_resolve and
+// rerank.hip k_rerank probe
 __global__ void k_idmap_build(const uint64_t *__restrict__ ids, uint32_t n, uint64_t *__restrict__ keys,
                               uint32_t *__restrict__ vals, uint32_t mask) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -227,179 +165,6 @@ __global__ void k_idmap_build(const uint64_t *__restrict__ ids, uint32_t n, uint
       return;
     }
     h = (h + 1) & mask;
-  }
-}
-template <bool MAP>
-__global__ __launch_bounds__(64) void k_filter_resolve(const uint64_t *__restrict__ ids, const uint32_t *__restrict__ off,
-                                                       uint64_t base_id, uint32_t view_n, uint32_t search_size,
-                                                       uint32_t *__restrict__ slots, uint32_t *__restrict__ fcnt,
-                                                       uint32_t *__restrict__ scnt, uint32_t *__restrict__ flags,
-                                                       const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                                       uint32_t mask) {
-  const uint32_t q = blockIdx.x;
-  const int lane = threadIdx.x;
-  const uint32_t b = off[q], e = off[q + 1];
-  uint32_t pos = 0, ns = 0;
-  bool bad = false, unsorted = false;
-  int64_t last = -1;  // MAP: the slot of the last id that resolved (wave-uniform)
-  for (uint32_t base = b; base < e; base += 64) {
-    const uint32_t i = base + lane;
-    const bool has = i < e;
-    const uint64_t id = has ? ids[i] : 0;
-    if (has && i > b && id <= ids[i - 1]) bad = true;
-    uint64_t s = id - base_id;
-    bool ok = has && id >= base_id && s < (uint64_t)view_n;  // rows past the committed count do not exist yet
-    if constexpr (MAP) {
-      ok = false;
-      if (has && id != 0) {
-        uint32_t h = idmap_hash(id) & mask;
-        while (true) {
-          const uint64_t k = keys[h];
-          if (k == id) {
-            s = vals[h], ok = true;
-            break;
-          }
-          if (k == 0) break;
-          h = (h + 1) & mask;
-        }
-      }
-    }
-    const uint64_t m = __ballot(ok);
-    if constexpr (MAP) {
-      if (m) {
-        const uint64_t below = m & ((1ull << lane) - 1);
-        const int prev_lane = below ? 63 - __clzll((long long)below) : lane;
-        const uint32_t sp = (uint32_t)__shfl((int)(uint32_t)s, prev_lane, 64);
-        const int64_t prev = below ? (int64_t)sp : last;
-        if (ok && (int64_t)s <= prev) unsorted = true;
-        last = (int64_t)(uint32_t)__shfl((int)(uint32_t)s, 63 - __clzll((long long)m), 64);
-      }
-    }
-    if (ok) slots[b + pos + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = (uint32_t)s;
-    if (base - b < search_size) {  // GetMany(first searchSize ids) skips the unknown ones (itemcache.go:109-128)
-      const uint32_t left = search_size - (base - b);
-      ns += (uint32_t)__popcll(left >= 64 ? m : (m & ((1ull << left) - 1)));
-    }
-    pos += (uint32_t)__popcll(m);
-  }
-  if (__ballot(bad) && lane == 0) atomicOr(flags, 1u), flags[1] = q;
-  if (MAP && __ballot(unsorted) && lane == 0) flags[2] = 1u;
-  if (lane == 0) fcnt[q] = pos, scnt[q] = ns;
-}
-
-// The same for a filter handed over as a BITMAP (sdb_index_search_batch_bitmap): bit i of query q's words is the id
-// first_id[q] + i.  A roaring bitmap keeps its dense chunks in exactly this form, and at 100 000 ids out of a million it is
-// an eighth of the bytes of the id list -- the upload is what a large filter costs.  Pass 1 (this kernel, one wave per
-// query, a lane per 64-bit word): how many of its bits name rows that exist (fcnt) and how many of its FIRST searchSize
-// bits do (scnt: the seeds are GetMany(first searchSize ids), unknown ids skipped, search.go:41-48).
-__device__ __forceinline__ uint64_t bitmap_valid_mask(uint64_t id0, uint64_t base_id, uint32_t view_n) {
-  // bits b of a word whose first id is id0 with base_id <= id0 + b < base_id + view_n  (ids wrap nowhere near 2^64 here)
-  uint64_t m = ~0ull;
-  if (id0 < base_id) {
-    const uint64_t skip = base_id - id0;
-    m = skip >= 64 ? 0ull : (m << skip);
-  }
-  const uint64_t end = base_id + view_n;  // first id past the table
-  if (id0 >= end) return 0ull;
-  const uint64_t room = end - id0;
-  if (room < 64) m &= (1ull << room) - 1;
-  return m;
-}
-__device__ __forceinline__ uint64_t lowest_set_bits(uint64_t w, uint32_t k) {  // the k lowest set bits of w (k < popc(w))
-  uint64_t out = 0;
-  for (uint32_t i = 0; i < k; i++) {
-    const uint64_t b = w & (0 - w);
-    out |= b, w ^= b;
-  }
-  return out;
-}
-template <bool ALL>  // ALL: every bit counts (the ids are resolved afterwards, k_filter_resolve<true>); scnt is not written
-__global__ __launch_bounds__(64) void k_filter_bitmap_count(const uint64_t *__restrict__ words, const uint32_t *__restrict__ woff,
-                                                            const uint64_t *__restrict__ first_id, uint64_t base_id,
-                                                            uint32_t view_n, uint32_t search_size, uint32_t *__restrict__ fcnt,
-                                                            uint32_t *__restrict__ scnt) {
-  const uint32_t q = blockIdx.x;
-  const int lane = threadIdx.x;
-  const uint32_t b = woff[q], e = woff[q + 1];
-  const uint64_t f0 = first_id[q];
-  uint32_t total = 0, seeds = 0, seen = 0;  // seen: set bits before this round of 64 words
-  for (uint32_t base = b; base < e; base += 64) {
-    const uint32_t w = base + lane;
-    const uint64_t word = w < e ? words[w] : 0ull;
-    const uint64_t valid = ALL ? word : (word & bitmap_valid_mask(f0 + (uint64_t)(w - b) * 64u, base_id, view_n));
-    uint32_t pc = (uint32_t)__popcll(word), incl = pc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {  // inclusive scan of the words' populations over the lanes
-      const uint32_t up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    const uint32_t before = seen + incl - pc;  // set bits of the filter in front of this word
-    if (before < search_size) {
-      const uint32_t left = search_size - before;
-      seeds += (uint32_t)__popcll(left >= pc ? valid : (valid & lowest_set_bits(word, left)));
-    }
-    total += (uint32_t)__popcll(valid);
-    seen += __shfl(incl, 63, 64);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o, 64), seeds += __shfl_down(seeds, o, 64);
-  if (lane == 0) {
-    fcnt[q] = total;
-    if (!ALL) scnt[q] = seeds;
-  }
-}
-// exclusive scan of the per-query counts -> where each query's slot list starts (one workgroup; nq is a batch size)
-__global__ __launch_bounds__(1024) void k_filter_offsets(const uint32_t *__restrict__ cnt, uint32_t nq, uint32_t *__restrict__ off,
-                                                          uint32_t *__restrict__ overflow) {
-  __shared__ uint64_t s_part[1024];
-  const uint32_t t = threadIdx.x, per = (nq + 1023) / 1024;
-  uint64_t sum = 0;
-  for (uint32_t i = t * per; i < min(nq, (t + 1) * per); i++) sum += cnt[i];
-  s_part[t] = sum;
-  __syncthreads();
-  if (t == 0) {
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < 1024; i++) {
-      const uint64_t v = s_part[i];
-      s_part[i] = run, run += v;
-    }
-    off[nq] = (uint32_t)run;
-    if (run > 0xFFFFFFFFull) *overflow = 1u;
-  }
-  __syncthreads();
-  uint64_t run = s_part[t];
-  for (uint32_t i = t * per; i < min(nq, (t + 1) * per); i++) off[i] = (uint32_t)run, run += cnt[i];
-}
-// pass 2: the slots, ascending, at the query's place in the list
-template <bool IDS>  // IDS: every bit, as the id it stands for (64-bit), for k_filter_resolve<true>
-__global__ __launch_bounds__(64) void k_filter_bitmap_expand(const uint64_t *__restrict__ words, const uint32_t *__restrict__ woff,
-                                                             const uint64_t *__restrict__ first_id, uint64_t base_id,
-                                                             uint32_t view_n, const uint32_t *__restrict__ off,
-                                                             uint32_t *__restrict__ slots, uint64_t *__restrict__ ids_out) {
-  const uint32_t q = blockIdx.x;
-  const int lane = threadIdx.x;
-  const uint32_t b = woff[q], e = woff[q + 1];
-  const uint64_t f0 = first_id[q];
-  uint32_t pos = off[q];
-  for (uint32_t base = b; base < e; base += 64) {
-    const uint32_t w = base + lane;
-    const uint64_t id0 = f0 + (uint64_t)(w - b) * 64u;
-    uint64_t valid = w < e ? (IDS ? words[w] : (words[w] & bitmap_valid_mask(id0, base_id, view_n))) : 0ull;
-    const uint32_t pc = (uint32_t)__popcll(valid);
-    uint32_t incl = pc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    uint32_t at = pos + incl - pc;
-    while (valid) {
-      const int bit = __ffsll((unsigned long long)valid) - 1;
-      valid &= valid - 1;
-      if constexpr (IDS) ids_out[at++] = id0 + (uint64_t)bit;
-      else slots[at++] = (uint32_t)(id0 + (uint64_t)bit - base_id);
-    }
-    pos += __shfl(incl, 63, 64);
   }
 }
 
@@ -684,18 +449,6 @@ using namespace sdb;
 // ------------------------------------------------------------------------------------------
 // sdb_index methods
 // ------------------------------------------------------------------------------------------
-int64_t sdb_index::slot_of(uint64_t id) const {
-  if (n == 0) return -1;
-  if (dense_ids) {
-    uint64_t base = h_ids[0];
-    if (id < base || id - base >= n) return -1;
-    return (int64_t)(id - base);
-  }
-  auto it = id2slot.find(id);
-  // (an insert in progress has entered its ids at the slots they will have: rows past n are not there yet)
-  return it == id2slot.end() || it->second >= n ? -1 : (int64_t)it->second;
-}
-
 int sdb_index::reserve(uint32_t rows) {
   if (rows <= cap) return SDB_OK;
   uint32_t ncap = cap ? cap : 1024;
@@ -1170,15 +923,6 @@ int sdb_index::ensure_idmap(const View &vw, hipStream_t stream) const {
   return SDB_OK;
 }
 
-int64_t sdb_index::slot_of_committed(uint64_t id, uint32_t view_n) const {
-  int64_t s = slot_of(id);
-  if ((s < 0 || (uint32_t)s >= view_n) && in_tx) {  // removed or replaced by the open transaction: the committed row is still there for a search on the committed graph
-    auto it = tx_deleted.find(id);
-    if (it != tx_deleted.end()) s = (int64_t)it->second;
-  }
-  return (s >= 0 && (uint32_t)s < view_n) ? s : -1;  // rows past the committed count belong to the transaction
-}
-
 int sdb_index::alloc_adjcodes() {
   if (d_adjcodes) (void)hipFree(d_adjcodes);
   if (r_adjcodes) (void)hipFree(r_adjcodes);
@@ -1429,7 +1173,7 @@ struct PinnedRange {
 static std::shared_mutex g_pinned_mu;
 static std::map<uintptr_t, PinnedRange> g_pinned;
 
-static bool device_view_of_host(const void *p, size_t bytes, void **dev) {
+bool sdb::device_view_of_host(const void *p, size_t bytes, void **dev) {
   const uintptr_t a = reinterpret_cast<uintptr_t>(p);
   {
     std::shared_lock<std::shared_mutex> g(g_pinned_mu);
@@ -1799,519 +1543,6 @@ int sdb_index_version_diff(const sdb_index *ix, uint64_t *rows) try {
   return SDB_OK;
 }
 SDB_API_CATCH("sdb_index_version_diff")
-
-// a filter handed over as bitmaps (sdb_index_search_batch_bitmap)
-struct BitmapFilters {
-  const uint64_t *first_id, *word_offsets, *words;
-};
-constexpr int kBitmapNeedsIds = -7001;  // search_batch_impl: this table cannot take bitmaps on the device; the caller expands them
-
-static int search_batch_impl(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit,
-                             uint32_t search_size, const uint64_t *filter_offsets,
-                             const uint64_t *filter_ids, const BitmapFilters *bm, uint64_t *out_ids, float *out_dists,
-                             uint32_t *out_counts, const sdb_search_trace *trace, int mem, void *stream_,
-                             uint32_t rerank = 0) {
-  // rerank != 0 (sdb_index_search_batch_rerank): the walk is launched exactly as without it, with limit = rerank and its
-  // three outputs in the workspace; k_rerank (rerank.hip) then writes where the walk would have written
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (nq == 0) return SDB_OK;
-  if (!queries || !out_ids || !out_dists || !out_counts) return fail(SDB_ERR_INVALID, "NULL argument");
-  if (limit < 1) return fail(SDB_ERR_INVALID, "invalid limit %u for vector query", limit);
-  if (search_size < limit)  // search.go:23-25
-    return fail(SDB_ERR_INVALID, "searchSize (%u) must be greater than k (%u)", search_size, limit);
-  if (rerank && (rerank < limit || rerank > search_size))
-    return fail(SDB_ERR_INVALID, "rerank (%u) must lie between k (%u) and searchSize (%u)", rerank, limit, search_size);
-  if (rerank && search_size > kRerankMax)
-    return fail(SDB_ERR_INVALID, "searchSize %u not supported on device (1..512)", search_size);
-  if (ix->P.strict && (search_size < 25 || search_size > 75 || limit > 75))  // models/search.go:287-297
-    return fail(SDB_ERR_INVALID, "invalid searchSize %u / limit %u for vector query, expected 25-75 / 1-75",
-                search_size, limit);
-  if (ix->broken) return fail(SDB_ERR_STATE, "index is unusable after a failed write; reload it from the bucket");
-  if (ix->start_slot < 0) return fail(SDB_ERR_STATE, "failed to get start point");  // search.go:57-60
-  const bool filtered = filter_offsets != nullptr || bm != nullptr;
-  if (filter_offsets && filter_offsets[nq] && !filter_ids) return fail(SDB_ERR_INVALID, "filter_ids is NULL");
-  if (nq > 0x7FFFFFFFull) return fail(SDB_ERR_INVALID, "too many queries");
-  DeviceGuard dg(ix->P.device);
-  hipStream_t stream = as_stream(stream_);
-  const bool async = mem == SDB_MEM_DEVICE;
-  Workspace *ws = ix->acquire_ws(stream, async);
-  struct Rel {
-    const sdb_index *ix;
-    Workspace *ws;
-    hipStream_t stream;
-    bool async;
-    ~Rel() { ix->release_ws(ws, stream, async); }
-  } rel{ix, ws, stream, async};
-  if (mem == SDB_MEM_HOST) {
-    if (!ws->own_stream) SDB_HIP(hipStreamCreateWithFlags(&ws->own_stream, hipStreamNonBlocking));
-    stream = ws->own_stream;
-  }
-  const RowLayout &l = ix->lay;
-  // the graph version this batch walks: the last committed one, whatever a writer is doing meanwhile.  The shared
-  // lock is held until the kernels are enqueued and their event recorded (sdb_index::commit counts on that).
-  std::shared_lock<sdb::ViewMutex> rl(ix->view_mu);
-  const sdb_index::View vw = ix->view;
-  const uint32_t words = ((vw.n + 31) / 32 + 31) & ~31u;  // per-query bitset, 128-byte multiple
-  const size_t bs_bytes = (size_t)nq * words * sizeof(uint32_t);
-  SDB_TRY(ws->ensure_bitsets(filtered ? 2 * bs_bytes : bs_bytes));
-  // re-ranking: the walk's candidates stay in the workspace, and their ids become slots again on the device -- by the
-  // committed view's id -> slot table where the ids are not consecutive (built here, before anything is enqueued)
-  RerankArgs ra{};
-  float *rr_dists = nullptr;
-  if (rerank) {
-    const size_t b_ids = ((size_t)nq * rerank * sizeof(uint64_t) + 255) & ~(size_t)255;
-    const size_t b_d = ((size_t)nq * rerank * sizeof(float) + 255) & ~(size_t)255;
-    SDB_TRY(ws->ensure_rerank(b_ids + b_d + nq * sizeof(uint32_t)));
-    if (!ix->dense_ids) {
-      SDB_TRY(ix->ensure_idmap(vw, stream));
-      ra.keys = ix->idmap.keys, ra.vals = ix->idmap.vals, ra.mask = ix->idmap.cells - 1;
-    }
-    char *rb = static_cast<char *>(ws->rerank);
-    ra.cand_ids = reinterpret_cast<uint64_t *>(rb), ra.cand_cnt = reinterpret_cast<uint32_t *>(rb + b_ids + b_d);
-    rr_dists = reinterpret_cast<float *>(rb + b_ids);  // (the quantizer's distances: written by the walk, read by nobody)
-    ra.base_id = ix->h_ids.empty() ? 0 : ix->h_ids[0], ra.view_n = vw.n;
-    ra.slab = ix->d_slab, ra.dim = l.dim, ra.nblk = l.nblk, ra.ng = l.ng, ra.tail = l.tail, ra.ld = l.ld;
-    ra.rerank = rerank, ra.limit = limit, ra.metric = (int)ix->P.metric;
-  }
-
-  SearchArgs a{};
-  a.slab = ix->d_slab, a.adj = vw.adj, a.ids = vw.ids;
-  a.adj_codes = vw.adj_codes, a.adj_rows = vw.n;
-  a.bitsets = ws->bitsets, a.words_per_query = words;
-  if (bm) {
-    // bitmaps: two passes on the device (count, expand) turn them into the same ascending slot lists; only for a table
-    // with consecutive ids, where id -> slot is a subtraction
-    if (ix->n == 0 || vw.n == 0 || ix->tune_host_filters) return kBitmapNeedsIds;
-    // a table whose ids are not consecutive: the bitmaps become id lists ON THE DEVICE (every bit, as the id it stands
-    // for) and those are resolved through the committed view's id -> slot table like uploaded id lists are
-    const bool by_map = !ix->dense_ids;
-    if (by_map && ix->ensure_idmap(vw, stream) != SDB_OK) return kBitmapNeedsIds;
-    for (uint64_t q = 0; q < nq; q++)
-      if (bm->word_offsets[q + 1] < bm->word_offsets[q]) return fail(SDB_ERR_INVALID, "filter_word_offsets must be non-decreasing");
-    const uint64_t total_words = bm->word_offsets[nq] - bm->word_offsets[0];
-    if (total_words >= (1ull << 32)) return fail(SDB_ERR_INVALID, "filter bitmaps of one batch are limited to 2^32 words");
-    const uint64_t base_id = ix->h_ids[0];
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_off = up((nq + 1) * 4), b_first = up(nq * 8), b_words = up(total_words * 8), b_cnt = up(nq * 4);
-    SDB_TRY(ws->ensure_filter_host(b_off + 256));
-    SDB_TRY(ws->ensure_filter_aux(2 * b_off + b_first + b_words + 2 * b_cnt + 256));
-    char *fb = static_cast<char *>(ws->filter_aux);
-    uint32_t *d_woff = (uint32_t *)fb, *d_off = (uint32_t *)(fb + b_off);
-    uint64_t *d_first = (uint64_t *)(fb + 2 * b_off), *d_words = (uint64_t *)(fb + 2 * b_off + b_first);
-    uint32_t *d_fc = (uint32_t *)(fb + 2 * b_off + b_first + b_words), *d_sc = (uint32_t *)((char *)d_fc + b_cnt);
-    uint32_t *d_flags = (uint32_t *)((char *)d_sc + b_cnt);
-    uint32_t *h_off = static_cast<uint32_t *>(ws->filter_host);
-    uint32_t *h_back = h_off + (nq + 1) + 2;  // [0] total slots, [1] overflow
-    for (uint64_t q = 0; q <= nq; q++) h_off[q] = (uint32_t)(bm->word_offsets[q] - bm->word_offsets[0]);
-    SDB_HIP(hipMemcpyAsync(d_woff, h_off, (nq + 1) * 4, hipMemcpyHostToDevice, stream));
-    SDB_HIP(hipMemcpyAsync(d_first, bm->first_id, nq * 8, hipMemcpyHostToDevice, stream));
-    if (total_words)
-      SDB_HIP(hipMemcpyAsync(d_words, bm->words + bm->word_offsets[0], total_words * 8, hipMemcpyHostToDevice, stream));
-    SDB_HIP(hipMemsetAsync(d_flags, 0, 16, stream));
-    if (by_map)
-      hipLaunchKernelGGL(k_filter_bitmap_count<true>, dim3((unsigned)nq), dim3(64), 0, stream, d_words, d_woff, d_first, base_id, vw.n,
-                         search_size, d_fc, d_sc);
-    else
-      hipLaunchKernelGGL(k_filter_bitmap_count<false>, dim3((unsigned)nq), dim3(64), 0, stream, d_words, d_woff, d_first, base_id, vw.n,
-                         search_size, d_fc, d_sc);
-    hipLaunchKernelGGL(k_filter_offsets, dim3(1), dim3(1024), 0, stream, d_fc, (uint32_t)nq, d_off, d_flags);
-    SDB_HIP(hipGetLastError());
-    SDB_HIP(hipMemcpyAsync(h_back, d_off + nq, 4, hipMemcpyDeviceToHost, stream));
-    SDB_HIP(hipMemcpyAsync(h_back + 1, d_flags, 4, hipMemcpyDeviceToHost, stream));
-    SDB_HIP(hipStreamSynchronize(stream));  // the slot list's size; the caller's arrays are free again
-    if (h_back[1]) return fail(SDB_ERR_INVALID, "the filters of one batch name more than 2^32 stored ids");
-    const size_t b_sl = up((size_t)h_back[0] * 4);
-    SDB_TRY(ws->ensure_filter(b_sl + (by_map ? (size_t)h_back[0] * 8 : 0) + 256));
-    uint32_t *d_sl = static_cast<uint32_t *>(ws->filter);
-    if (by_map) {
-      uint64_t *d_ids64 = reinterpret_cast<uint64_t *>(static_cast<char *>(ws->filter) + b_sl);
-      hipLaunchKernelGGL(k_filter_bitmap_expand<true>, dim3((unsigned)nq), dim3(64), 0, stream, d_words, d_woff, d_first, base_id, vw.n,
-                         d_off, d_sl, d_ids64);
-      // d_flags[0] is the offsets' overflow word (zero here); the resolve kernel's three words follow it
-      hipLaunchKernelGGL(k_filter_resolve<true>, dim3((unsigned)nq), dim3(64), 0, stream, d_ids64, d_off, base_id, vw.n, search_size, d_sl,
-                         d_fc, d_sc, d_flags + 1, ix->idmap.keys, ix->idmap.vals, ix->idmap.cells - 1);
-      SDB_HIP(hipGetLastError());
-      SDB_HIP(hipMemcpyAsync(h_back, d_flags + 3, 4, hipMemcpyDeviceToHost, stream));
-      SDB_HIP(hipStreamSynchronize(stream));
-      if (h_back[0]) a.filt_ids = d_ids64;  // ids and slots disagree on the order somewhere: Contains by id (search_kernel.h)
-    } else {
-      hipLaunchKernelGGL(k_filter_bitmap_expand<false>, dim3((unsigned)nq), dim3(64), 0, stream, d_words, d_woff, d_first, base_id, vw.n,
-                         d_off, d_sl, nullptr);
-      SDB_HIP(hipGetLastError());
-    }
-    a.seed_off = d_off, a.filt_off = d_off, a.seeds = d_sl, a.filt_slots = d_sl, a.seed_cnt = d_sc, a.filt_cnt = d_fc;
-    a.rbitsets = ws->bitsets + (size_t)nq * words;
-  } else if (filtered) {
-    // search.go:41-48: seeds = the first <= searchSize filter ids (ascending) that exist; Contains (:93) is
-    // answered from the whole filter as ascending slots.  Filter arrays are host memory (header).
-    const uint64_t total_ids = filter_offsets[nq] - filter_offsets[0];
-    bool on_device = false;
-    {
-      // Consecutive ids (the bulk-loaded and append-only table: id = first id + slot, no holes): the ids go up as they
-      // are and one wave per query turns them into slots on the device.  What the host did for this -- a hash lookup per
-      // id on up to 16 threads, two passes, an upload of the slots -- cost 1.2 ms per batch at 1 000 ids per query next
-      // to a 1.5 ms walk, 26 ms at 100 000.  The ids of the open transaction's appended rows resolve to slots past the
-      // committed count and are dropped; deletes end the table's consecutiveness (the table below takes over).
-      // (the id tables only change under the view lock, which this call holds shared)
-      on_device = ix->n > 0 && vw.n > 0 && total_ids < (1ull << 32) && !ix->tune_host_filters;
-    }
-    // Any other table (deletes left holes, arbitrary ids): the same kernel probes the committed view's id -> slot
-    // table, built on the device by the first filtered search of the view (sdb_index::IdMap).
-    const bool by_map = on_device && !ix->dense_ids;
-    if (by_map && ix->ensure_idmap(vw, stream) != SDB_OK) on_device = false;  // no memory for the table: the host's map
-    if (on_device) {
-      for (uint64_t q = 0; q < nq; q++)
-        if (filter_offsets[q + 1] < filter_offsets[q]) return fail(SDB_ERR_INVALID, "filter_offsets must be non-decreasing");
-      const uint64_t base_id = ix->h_ids[0];
-      const size_t b_off = ((nq + 1) * 4 + 255) & ~(size_t)255, b_ids = (total_ids * 8 + 255) & ~(size_t)255;
-      const size_t b_sl = (total_ids * 4 + 255) & ~(size_t)255, b_cnt = (nq * 4 + 255) & ~(size_t)255;
-      SDB_TRY(ws->ensure_filter(b_off + b_ids + b_sl + 2 * b_cnt + 256));
-      SDB_TRY(ws->ensure_filter_host(b_off + 256));
-      char *fb = static_cast<char *>(ws->filter);
-      uint32_t *d_off = (uint32_t *)fb;
-      uint64_t *d_raw = (uint64_t *)(fb + b_off);
-      uint32_t *d_sl = (uint32_t *)(fb + b_off + b_ids);
-      uint32_t *d_fc = (uint32_t *)(fb + b_off + b_ids + b_sl), *d_sc = (uint32_t *)(fb + b_off + b_ids + b_sl + b_cnt);
-      uint32_t *d_flags = (uint32_t *)(fb + b_off + b_ids + b_sl + 2 * b_cnt);
-      uint32_t *h_off = static_cast<uint32_t *>(ws->filter_host);
-      uint32_t *h_flags = h_off + (nq + 1) + 2;
-      for (uint64_t q = 0; q <= nq; q++) h_off[q] = (uint32_t)(filter_offsets[q] - filter_offsets[0]);
-      SDB_HIP(hipMemcpyAsync(d_off, h_off, (nq + 1) * 4, hipMemcpyHostToDevice, stream));
-      // straight from the caller's array: one DMA when it is pinned (sdb_host_alloc), a staged copy otherwise
-      if (total_ids) SDB_HIP(hipMemcpyAsync(d_raw, filter_ids + filter_offsets[0], total_ids * 8, hipMemcpyHostToDevice, stream));
-      SDB_HIP(hipMemsetAsync(d_flags, 0, 12, stream));
-      if (by_map)
-        hipLaunchKernelGGL(k_filter_resolve<true>, dim3((unsigned)nq), dim3(64), 0, stream, d_raw, d_off, base_id, vw.n, search_size, d_sl,
-                           d_fc, d_sc, d_flags, ix->idmap.keys, ix->idmap.vals, ix->idmap.cells - 1);
-      else
-        hipLaunchKernelGGL(k_filter_resolve<false>, dim3((unsigned)nq), dim3(64), 0, stream, d_raw, d_off, base_id, vw.n, search_size, d_sl,
-                           d_fc, d_sc, d_flags, nullptr, nullptr, 0u);
-      SDB_HIP(hipGetLastError());
-      SDB_HIP(hipMemcpyAsync(h_flags, d_flags, 12, hipMemcpyDeviceToHost, stream));
-      SDB_HIP(hipStreamSynchronize(stream));  // the caller's arrays are free again; an invalid filter is an error, not a search
-      if (h_flags[0])
-        return fail(SDB_ERR_INVALID, "filter ids of query %llu are not strictly ascending", (unsigned long long)h_flags[1]);
-      a.seed_off = d_off, a.filt_off = d_off, a.seeds = d_sl, a.filt_slots = d_sl, a.seed_cnt = d_sc, a.filt_cnt = d_fc;
-      // ids and slots disagree on the order somewhere (an id deleted and inserted again sits behind larger ids): the
-      // seeds are the first slots in ID order either way; Contains is answered from the ids themselves then
-      if (h_flags[2]) a.filt_ids = d_raw;
-      a.rbitsets = ws->bitsets + (size_t)nq * words;
-    }
-    std::vector<uint32_t> off_seed(on_device ? 0 : nq + 1, 0), off_filt(on_device ? 0 : nq + 1, 0);
-    if (!on_device) {
-    // ids -> slots is a hash lookup per id; a batch of 1 024 queries with 1 000-id filters carries a million of them
-    // (5 ms on one core), so big batches are split over a few host threads.  Pass 1 validates and counts, pass 2
-    // fills the two CSR arrays in place.
-    // one thread per 128 k ids, at most 16 (and what the machine has): a million ids take 5 ms on one core, a thread ~50 us to start
-    const unsigned nthr = (unsigned)std::min<uint64_t>(std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())),
-                                                       std::max<uint64_t>(1, total_ids >> 17));
-    std::vector<uint32_t> n_seed(nq, 0), n_filt(nq, 0);
-    std::atomic<int> bad{0};  // 1: offsets decrease, 2: ids not ascending
-    std::atomic<uint64_t> bad_q{0};
-    auto for_queries = [&](auto &&fn) {
-      if (nthr == 1) {
-        for (uint64_t q = 0; q < nq; q++) fn(q);
-        return;
-      }
-      // a thread that cannot be had (std::system_error, or no memory for its state) must not leave joinable threads
-      // behind -- their destructors would end the process: whatever did start is joined, the rest of the queries are
-      // done here
-      std::vector<std::thread> pool;
-      unsigned started = 0;
-      try {
-        pool.reserve(nthr);
-        for (; started < nthr; started++)
-          pool.emplace_back([&, t = started] {
-            for (uint64_t q = (uint64_t)nq * t / nthr; q < (uint64_t)nq * (t + 1) / nthr; q++) fn(q);
-          });
-      } catch (...) {
-      }
-      for (uint64_t q = (uint64_t)nq * started / nthr; q < nq; q++) fn(q);
-      for (auto &th : pool) th.join();
-    };
-    for_queries([&](uint64_t q) {
-      const uint64_t b = filter_offsets[q], e = filter_offsets[q + 1];
-      if (e < b) {
-        bad = 1;
-        return;
-      }
-      uint32_t ns = 0, nf = 0;
-      for (uint64_t i = b; i < e; i++) {
-        if (i > b && filter_ids[i] <= filter_ids[i - 1]) {
-          bad = 2, bad_q = q;
-          return;
-        }
-        if (ix->slot_of_committed(filter_ids[i], vw.n) < 0) continue;  // GetMany skips unknown ids (itemcache.go:109-128)
-        if (i - b < search_size) ns++;
-        nf++;
-      }
-      n_seed[q] = ns, n_filt[q] = nf;
-    });
-    if (bad == 1) return fail(SDB_ERR_INVALID, "filter_offsets must be non-decreasing");
-    if (bad == 2) return fail(SDB_ERR_INVALID, "filter ids of query %llu are not strictly ascending", (unsigned long long)bad_q.load());
-    for (uint64_t q = 0; q < nq; q++) off_seed[q + 1] = off_seed[q] + n_seed[q], off_filt[q + 1] = off_filt[q] + n_filt[q];
-    // the two lists are written where the DMA engine can take them from (pinned, kept with the workspace): a pageable
-    // vector of 10^8 slots costs its zero-fill and a staged copy on top of the translation
-    const size_t n_seeds = off_seed[nq], n_fslots = off_filt[nq];
-    const size_t h_seeds = (n_seeds * 4 + 255) & ~(size_t)255;
-    std::unique_ptr<char[]> pageable;  // when the pinned buffer cannot be had (the limit on locked memory): an ordinary one
-    char *hbase = nullptr;
-    if (ws->ensure_filter_host(h_seeds + n_fslots * 4 + 256) == SDB_OK) {
-      hbase = static_cast<char *>(ws->filter_host);
-    } else {
-      (void)hipGetLastError();
-      pageable.reset(new (std::nothrow) char[h_seeds + n_fslots * 4 + 256]);
-      if (!pageable) return fail(SDB_ERR_DEVICE, "out of host memory for the filter lists");
-      hbase = pageable.get();
-    }
-    uint32_t *seeds_h = reinterpret_cast<uint32_t *>(hbase);
-    uint32_t *fslots_h = reinterpret_cast<uint32_t *>(hbase + h_seeds);
-    for_queries([&](uint64_t q) {
-      const uint64_t b = filter_offsets[q], e = filter_offsets[q + 1];
-      uint32_t *sp = seeds_h + off_seed[q], *fp = fslots_h + off_filt[q];
-      bool ascending = true;  // rows stored in id order (the usual case) translate to ascending slots: nothing to sort
-      int64_t last = -1;
-      for (uint64_t i = b; i < e; i++) {
-        const int64_t s = ix->slot_of_committed(filter_ids[i], vw.n);
-        if (s < 0) continue;
-        if (i - b < search_size) *sp++ = (uint32_t)s;  // search.go:41-48: the first <= searchSize filter ids that exist
-        *fp++ = (uint32_t)s;
-        ascending &= s > last;
-        last = s;
-      }
-      if (!ascending) std::sort(fslots_h + off_filt[q], fp);  // Contains (:93) is answered from ascending slots
-    });
-    const size_t b_off = (nq + 1) * 4, b_seeds = n_seeds * 4, b_f = n_fslots * 4;
-    SDB_TRY(ws->ensure_filter(2 * ((b_off + 255) & ~(size_t)255) + ((b_seeds + 255) & ~(size_t)255) + b_f + 256));
-    char *fb = static_cast<char *>(ws->filter);
-    uint32_t *d_so = (uint32_t *)fb;
-    uint32_t *d_fo = (uint32_t *)(fb + ((b_off + 255) & ~(size_t)255));
-    uint32_t *d_seeds = (uint32_t *)(fb + 2 * ((b_off + 255) & ~(size_t)255));
-    uint32_t *d_f = (uint32_t *)((char *)d_seeds + ((b_seeds + 255) & ~(size_t)255));
-    SDB_HIP(hipMemcpyAsync(d_so, off_seed.data(), b_off, hipMemcpyHostToDevice, stream));
-    SDB_HIP(hipMemcpyAsync(d_fo, off_filt.data(), b_off, hipMemcpyHostToDevice, stream));
-    if (b_seeds) SDB_HIP(hipMemcpyAsync(d_seeds, seeds_h, b_seeds, hipMemcpyHostToDevice, stream));
-    if (b_f) SDB_HIP(hipMemcpyAsync(d_f, fslots_h, b_f, hipMemcpyHostToDevice, stream));
-    SDB_HIP(hipStreamSynchronize(stream));  // the staging vectors die with this scope
-    a.seed_off = d_so, a.filt_off = d_fo, a.seeds = d_seeds, a.filt_slots = d_f;
-    a.rbitsets = ws->bitsets + (size_t)nq * words;
-    }
-  }
-  a.dim = l.dim, a.nblk = l.nblk, a.ng = l.ng, a.tail = l.tail, a.ld = l.ld;
-  a.start_slot = (uint32_t)ix->start_slot;
-  a.start_ext = vw.start_ext, a.start_ext_n = vw.start_ext_n;
-  a.search_size = search_size, a.limit = rerank ? rerank : limit, a.metric = (int)ix->P.metric;
-  a.hash_limit = ix->tune_hash_limit, a.prefer_bitset = ix->tune_no_hash ? 1u : 0u;
-  a.wide_hash = ix->tune_wide_hash ? 1u : 0u, a.hash16_probes = ix->tune_hash16_probes;
-  a.pq_narrow = ix->tune_pq_narrow;
-  a.wide_mode = ix->tune_wide_walk;
-  // two-precision hop: only with the copy of exactly this view's rows, outside a write transaction.  Every field is read
-  // once, under the shared lock the writer's changes to them exclude.  This call's stage is decided here, once: the int8
-  // copy serves the calls stage_int8() names (a filtered call reads float32 rows then), the float16 copy every plain
-  // call and -- opt-in, SDB_TUNE_SKETCH_FILTERED -- the filtered ones.
-  {
-    const uint32_t knob = ix->tune_sketch;
-    const void *sk = ix->d_sketch;
-    if (knob && sk && ix->sketch_gen.load(std::memory_order_acquire) == ix->view_gen && !ix->in_tx) {
-      if (ix->sketch8) a.stage = stage_int8((int)l.ng, ix->P.metric == SDB_METRIC_EUCLIDEAN, filtered) ? Stage::kInt8 : Stage::kNone;
-      else a.stage = (!filtered || ix->tune_sketch_filtered) ? Stage::kHalf : Stage::kNone;
-    }
-    if (a.stage != Stage::kNone)
-      a.sketch = sk, a.sketch_norm = ix->d_sketch_norm, a.sk_emax = ix->sk_emax, a.sk_ymax = ix->sk_ymax,
-      a.sk_audit = (knob == 2 || knob == 4) ? 1u : 0u, a.sk_counters = ix->d_sk_counters, a.sk8_scale = ix->sk8_scale;
-  }
-
-  const uint32_t vcap = trace ? trace->visit_cap : 0;
-  auto launch = [&]() -> int {
-    if (ix->bq)  // DistanceFromFloat encodes the query once (binary.go:192): the walk does, when it starts (BitDist::init)
-      a.bq_codes = reinterpret_cast<const uint64_t *>(ix->d_codes), a.bq_thr = ix->bq->d_thr, a.bq_W = ix->bq->W,
-      a.bq_metric = (uint32_t)ix->bq->metric;
-    if (ix->pq) {  // fitted quantizer: DistanceFromFloat builds the M x K table first (product.go:255-263)
-      const sdb_pq *pq = ix->pq;
-      SDB_TRY(ws->ensure_lut((size_t)nq * pq->M * pq->K * sizeof(float)));
-      SDB_TRY(pq_build_lut(pq, a.queries, nq, ws->lut, stream));
-      a.pq_lut = ws->lut, a.pq_codes = ix->d_codes, a.pq_M = pq->M, a.pq_K = pq->K;
-      a.pq_lut_in_lds = ((size_t)pq->M * pq->K * sizeof(float) <= 64 * 1024) ? 1u : 0u;
-    }
-    // ClearAll (distset.go:101); the LDS hash variant clears a bitset only for a query that overflows it
-    if (!search_uses_hash(a, (uint32_t)nq) && !sketch_walk(a, (uint32_t)nq))
-      SDB_HIP(hipMemsetAsync(ws->bitsets, 0, filtered ? 2 * bs_bytes : bs_bytes, stream));
-    if (rerank) {  // the walk's outputs go to the workspace; what the caller (or the staging below) named is k_rerank's to write
-      ra.queries = a.queries, ra.out_ids = a.out_ids, ra.out_dists = a.out_dists, ra.out_counts = a.out_counts;
-      a.out_ids = const_cast<uint64_t *>(ra.cand_ids), a.out_dists = rr_dists, a.out_counts = const_cast<uint32_t *>(ra.cand_cnt);
-    }
-    const bool prof = ix->profiling && !ix->ev0.empty();
-    const uint32_t slot = (uint32_t)(ix->prof_count % sdb_index::kProfRing);
-    if (prof) (void)hipEventRecord(ix->ev0[slot], stream);
-    int rc = launch_greedy_search(a, (uint32_t)nq, stream);
-    if (prof) {
-      (void)hipEventRecord(ix->ev1[slot], stream);
-      ix->prof_count++;
-    }
-    if (rerank) a.out_ids = ra.out_ids, a.out_dists = ra.out_dists, a.out_counts = ra.out_counts;  // (the copies below read these)
-    if (rerank && rc == SDB_OK) {  // same stream, same view, still under the shared lock: no commit comes between the two
-      const uint32_t slot2 = (uint32_t)(ix->prof_count % sdb_index::kProfRing);  // a profiled call records two entries: walk, re-rank
-      if (prof) (void)hipEventRecord(ix->ev0[slot2], stream);
-      rc = launch_rerank(ra, (uint32_t)nq, stream);
-      if (prof) {
-        (void)hipEventRecord(ix->ev1[slot2], stream);
-        ix->prof_count++;
-      }
-      // the id -> slot table is this view's only while the shared lock is held (sdb_index::IdMap: the next view's first
-      // filtered or re-ranked search rebuilds it in place): like k_filter_resolve, the probe has run before the lock goes
-      if (ra.keys && rc == SDB_OK && hipStreamSynchronize(stream) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(SDB_ERR_DEVICE, "re-ranked search failed on the device");
-      }
-    }
-    // from here on a commit may hand the copy this batch walks to the writer: it waits for this event first
-    if (!ws->launched) (void)hipEventCreateWithFlags(&ws->launched, hipEventDisableTiming);
-    if (ws->launched && hipEventRecord(ws->launched, stream) == hipSuccess) ws->launched_valid = true, ws->launched_is_tail = mem == SDB_MEM_DEVICE;
-    else if (rc == SDB_OK) (void)hipStreamSynchronize(stream);  // no event: finish before letting go of the version
-    rl.unlock();
-    return rc;
-  };
-  if (mem == SDB_MEM_DEVICE) {
-    a.queries = queries;
-    a.out_ids = out_ids, a.out_dists = out_dists, a.out_counts = out_counts;
-    if (trace) {
-      a.tr_ndist = trace->n_dist, a.tr_nhop = trace->n_hop, a.tr_nedges = trace->n_edges;
-      a.tr_visit = trace->visit_ids, a.visit_cap = trace->visit_ids ? vcap : 0;
-    }
-    return launch();
-  }
-  // host memory.  Page-locked buffers (sdb_host_alloc, or locked by the caller) are read and written IN PLACE by the
-  // walk: a wave reads its query once, when it starts (PlainDist::init), and writes its <= limit results when it ends,
-  // so what crosses the bus is what a copy would have moved, without the copy packets around the kernel and without a
-  // staging buffer -- the call is one launch and one wait.  (Not with a quantizer: the table kernel reads a query's
-  // sub-vectors once per centroid block, and host memory is not cached on the device.  Not with a trace: test calls.)
-  const bool zc_ok = !trace && !ix->tune_no_zero_copy;
-  void *z_q = nullptr, *z_i = nullptr, *z_d = nullptr, *z_c = nullptr;
-  const bool zc_out = zc_ok && device_view_of_host(out_ids, nq * limit * sizeof(uint64_t), &z_i) &&
-                      device_view_of_host(out_dists, nq * limit * sizeof(float), &z_d) &&
-                      device_view_of_host(out_counts, nq * sizeof(uint32_t), &z_c);
-  const bool zc_q = zc_ok && !ix->pq && !ix->bq && device_view_of_host(queries, nq * l.dim * sizeof(float), &z_q);
-  if (zc_out && zc_q) {
-    a.queries = static_cast<const float *>(z_q);
-    a.out_ids = static_cast<uint64_t *>(z_i), a.out_dists = static_cast<float *>(z_d), a.out_counts = static_cast<uint32_t *>(z_c);
-    SDB_TRY(launch());
-    SDB_HIP(hipStreamSynchronize(stream));
-    return SDB_OK;
-  }
-  // otherwise: stage through one scratch allocation (what is page-locked still skips its copy)
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_q = carve(nq * l.dim * sizeof(float));
-  const size_t o_ids = carve(nq * limit * sizeof(uint64_t));
-  const size_t o_d = carve(nq * limit * sizeof(float));
-  const size_t o_c = carve(nq * sizeof(uint32_t));
-  const size_t o_nd = carve(nq * sizeof(uint32_t)), o_nh = carve(nq * sizeof(uint32_t)),
-               o_ne = carve(nq * sizeof(uint32_t));
-  const size_t o_v = carve((trace && trace->visit_ids) ? nq * vcap * sizeof(uint64_t) : 0);
-  SDB_TRY(ws->ensure_scratch(off));
-  char *base = static_cast<char *>(ws->scratch);
-  if (zc_q) {
-    a.queries = static_cast<const float *>(z_q);
-  } else {
-    SDB_HIP(hipMemcpyAsync(base + o_q, queries, nq * l.dim * sizeof(float), hipMemcpyHostToDevice, stream));
-    a.queries = reinterpret_cast<float *>(base + o_q);
-  }
-  a.out_ids = reinterpret_cast<uint64_t *>(base + o_ids);
-  a.out_dists = reinterpret_cast<float *>(base + o_d);
-  a.out_counts = reinterpret_cast<uint32_t *>(base + o_c);
-  if (zc_out) a.out_ids = static_cast<uint64_t *>(z_i), a.out_dists = static_cast<float *>(z_d), a.out_counts = static_cast<uint32_t *>(z_c);
-  if (trace) {
-    a.tr_ndist = reinterpret_cast<uint32_t *>(base + o_nd);
-    a.tr_nhop = reinterpret_cast<uint32_t *>(base + o_nh);
-    a.tr_nedges = reinterpret_cast<uint32_t *>(base + o_ne);
-    if (trace->visit_ids) a.tr_visit = reinterpret_cast<uint64_t *>(base + o_v), a.visit_cap = vcap;
-  }
-  SDB_HIP(hipMemsetAsync(base + o_ids, 0, o_c - o_ids, stream));
-  SDB_TRY(launch());
-  if (!zc_out) {
-    SDB_HIP(hipMemcpyAsync(out_ids, a.out_ids, nq * limit * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    SDB_HIP(hipMemcpyAsync(out_dists, a.out_dists, nq * limit * sizeof(float), hipMemcpyDeviceToHost, stream));
-    SDB_HIP(hipMemcpyAsync(out_counts, a.out_counts, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  }
-  if (trace) {
-    if (trace->n_dist) SDB_HIP(hipMemcpyAsync(trace->n_dist, a.tr_ndist, nq * 4, hipMemcpyDeviceToHost, stream));
-    if (trace->n_hop) SDB_HIP(hipMemcpyAsync(trace->n_hop, a.tr_nhop, nq * 4, hipMemcpyDeviceToHost, stream));
-    if (trace->n_edges) SDB_HIP(hipMemcpyAsync(trace->n_edges, a.tr_nedges, nq * 4, hipMemcpyDeviceToHost, stream));
-    if (trace->visit_ids)
-      SDB_HIP(hipMemcpyAsync(trace->visit_ids, a.tr_visit, nq * vcap * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-  }
-  SDB_HIP(hipStreamSynchronize(stream));
-  return SDB_OK;
-}
-
-int sdb_index_search_batch(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit,
-                           uint32_t search_size, const uint64_t *filter_offsets,
-                           const uint64_t *filter_ids, uint64_t *out_ids, float *out_dists,
-                           uint32_t *out_counts, const sdb_search_trace *trace, int mem, void *stream_) try {
-  return search_batch_impl(ix, nq, queries, limit, search_size, filter_offsets, filter_ids, nullptr, out_ids, out_dists, out_counts,
-                           trace, mem, stream_);
-}
-SDB_API_CATCH("sdb_index_search_batch")
-
-// sdb_index_search_batch_bitmap and its re-ranked form (rerank != 0)
-static int search_batch_bitmap_impl(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
-                                    const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
-                                    const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
-                                    const sdb_search_trace *trace, int mem, void *stream_, uint32_t rerank) {
-  if (!filter_first_id || !filter_word_offsets) return fail(SDB_ERR_INVALID, "NULL filter argument");
-  if (nq && filter_word_offsets[nq] > filter_word_offsets[0] && !filter_words) return fail(SDB_ERR_INVALID, "filter_words is NULL");
-  const BitmapFilters bm{filter_first_id, filter_word_offsets, filter_words};
-  const int rc = search_batch_impl(ix, nq, queries, limit, search_size, nullptr, nullptr, &bm, out_ids, out_dists, out_counts, trace,
-                                   mem, stream_, rerank);
-  if (rc != kBitmapNeedsIds) return rc;
-  // a table whose ids are not consecutive (deletes, arbitrary ids): the host's hash map resolves ids, so the bitmaps
-  // become id lists here -- the reference iterates its roaring bitmap the same way (search.go:41-48)
-  std::vector<uint64_t> off(nq + 1, 0), ids;
-  for (uint64_t q = 0; q < nq; q++) {
-    if (filter_word_offsets[q + 1] < filter_word_offsets[q]) return fail(SDB_ERR_INVALID, "filter_word_offsets must be non-decreasing");
-    for (uint64_t w = filter_word_offsets[q]; w < filter_word_offsets[q + 1]; w++)
-      for (uint64_t word = filter_words[w]; word; word &= word - 1)
-        ids.push_back(filter_first_id[q] + (w - filter_word_offsets[q]) * 64 + (uint64_t)__builtin_ctzll(word));
-    off[q + 1] = ids.size();
-  }
-  if (ids.empty()) ids.push_back(0);
-  return search_batch_impl(ix, nq, queries, limit, search_size, off.data(), ids.data(), nullptr, out_ids, out_dists, out_counts, trace,
-                           mem, stream_, rerank);
-}
-
-int sdb_index_search_batch_bitmap(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
-                                  const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
-                                  const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
-                                  const sdb_search_trace *trace, int mem, void *stream_) try {
-  return search_batch_bitmap_impl(ix, nq, queries, limit, search_size, filter_first_id, filter_word_offsets, filter_words, out_ids,
-                                  out_dists, out_counts, trace, mem, stream_, 0);
-}
-SDB_API_CATCH("sdb_index_search_batch_bitmap")
-
-// The library's own extension (the reference does not re-rank): the walk's first `rerank` candidates in the order of
-// their stored float32 rows' distances (semadb_amd.h; rerank.hip).  rerank = 0 is no re-ranked search.
-int sdb_index_search_batch_rerank(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
-                                  uint32_t rerank, const uint64_t *filter_offsets, const uint64_t *filter_ids, uint64_t *out_ids,
-                                  float *out_dists, uint32_t *out_counts, const sdb_search_trace *trace, int mem, void *stream_) try {
-  if (rerank == 0) return fail(SDB_ERR_INVALID, "rerank (0) must lie between k (%u) and searchSize (%u)", limit, search_size);
-  return search_batch_impl(ix, nq, queries, limit, search_size, filter_offsets, filter_ids, nullptr, out_ids, out_dists, out_counts,
-                           trace, mem, stream_, rerank);
-}
-SDB_API_CATCH("sdb_index_search_batch_rerank")
-
-int sdb_index_search_batch_bitmap_rerank(sdb_index *ix, uint64_t nq, const float *queries, uint32_t limit, uint32_t search_size,
-                                         uint32_t rerank, const uint64_t *filter_first_id, const uint64_t *filter_word_offsets,
-                                         const uint64_t *filter_words, uint64_t *out_ids, float *out_dists, uint32_t *out_counts,
-                                         const sdb_search_trace *trace, int mem, void *stream_) try {
-  if (rerank == 0) return fail(SDB_ERR_INVALID, "rerank (0) must lie between k (%u) and searchSize (%u)", limit, search_size);
-  return search_batch_bitmap_impl(ix, nq, queries, limit, search_size, filter_first_id, filter_word_offsets, filter_words, out_ids,
-                                  out_dists, out_counts, trace, mem, stream_, rerank);
-}
-SDB_API_CATCH("sdb_index_search_batch_bitmap_rerank")
 
 int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
   if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");

@@ -4,7 +4,7 @@
 // The walk ran with limit = rerank and left, per query, up to `rerank` ids in its own order (quantizer distances).
 // One workgroup of four waves per query: the query tile goes to LDS in the slab's element order (as in
 // distance.hip k_index_distance), the ids become slots (a subtraction, or a probe of the view's id -> slot table as
-// index.hip k_filter_resolve probes it), every wave takes chunks of 2 U candidates through chunk_dist_lds -- the
+// search_batch.hip k_filter_resolve probes it), every wave takes chunks of 2 U candidates through chunk_dist_lds -- the
 // reference's FMA chains, tail chain and reduce tree (dist_core.h), so the distances are plainStore.DistanceFromFloat's
 // bit for bit --, the <= 512 exact distances meet in LDS, and every candidate counts the candidates whose key
 // (isnan(e), e, walk position) is below its own: that count is its place.  IEEE compares: -0.0 and 0.0 tie, ties keep

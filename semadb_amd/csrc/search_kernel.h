@@ -75,7 +75,7 @@ struct SearchArgs {
   // filtered search (search.go:33-51,93-95): per query CSR of seeds (<= searchSize slots, ascending id
   // order) and of the whole filter as ascending slots; rbitsets = the result set's own visited set
   const uint32_t *seed_off, *seeds, *filt_off, *filt_slots;
-  // filter lists resolved on the device (index.hip k_filter_resolve): the counts are not offset differences then
+  // filter lists resolved on the device (search_batch.hip k_filter_resolve): the counts are not offset differences then
   // (segments keep the caller's offsets, unknown ids leave gaps at their ends); NULL: offset differences
   const uint32_t *seed_cnt, *filt_cnt;
   // != NULL: Contains (:93) is answered from the filter's IDS -- the uploaded lists, strictly ascending, at filt_off's
@@ -102,7 +102,7 @@ struct SearchArgs {
   const void *sketch;                // Stage::kHalf: rows of `ld` halves; Stage::kInt8: rows of `ld` bytes
   const float *sketch_norm;          // [rows] ||y16||^2 of every row (euclidean tables: d16 = ||q16||^2 + ||y16||^2 - 2 q16.y16)
   float sk_emax, sk_ymax;            // max over the rows of ||y - y16|| and of ||y16|| (k_sketch_rows), rounded up; the int8 copy's likewise
-  Stage stage;                       // this call's first stage, decided once where the arguments are filled (index.hip); kNone: `sketch` is NULL
+  Stage stage;                       // this call's first stage, decided once where the arguments are filled (search_batch.hip choose_stage); kNone: `sketch` is NULL
   float sk8_scale;                   // the int8 copy's scale s: y8 = clamp(rint(y / s), -127, 127)
   uint32_t sk_audit;                 // != 0: evaluate everything exactly as well and count decisions the exact distance contradicts
   unsigned long long *sk_counters;   // [0] += neighbours discarded on their float16 distance, [1] += contradicted ones (audit)

@@ -13,6 +13,8 @@
 //   (c) the exchange    GpuFanout + the collective skeleton over turnstile.h: concurrent requests, a failing shard, a
 //                       rank that never arrives (deadline, withdrawal, skip), destruction
 //   (d) IndexVamana     searches from many threads while writers run InsertUpdateDelete
+//   (e) filter lists    csrc/filter_host.h (the code search_batch.hip runs): a batch's filter ids -> seeds and ascending
+//                       slots on 1, 3 and 16 threads, against a single-threaded model; its two error answers
 // Every answer is checked against the request that asked for it (mock_expect).
 #include <algorithm>
 #include <atomic>
@@ -26,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../semadb_amd/csrc/filter_host.h"
 #include "../../semadb_amd/csrc/turnstile.h"
 #include "../../semadb_amd/csrc/view_mutex.h"
 #include "../../semadb_amd/host/semadb_host.hpp"
@@ -702,6 +705,105 @@ static void test_vamana_readers_and_writers() {
   CHECK(!ix.Exists(10), "a deleted point");
 }
 
+// ---- (e) the host's filter translation (csrc/filter_host.h) ---------------------------------------------------
+// every fifth id names no row; `reused`: an id with id % 7 == 3 was deleted and inserted again, so its row lies behind
+// those of all larger ids -- ascending ids are then not ascending slots, and pass 2 has to sort
+static int64_t filter_slot_of(uint64_t id, bool reused) {
+  if (id % 5 == 0) return -1;
+  return (int64_t)(reused && id % 7 == 3 ? 1000000 + id : id);
+}
+
+// per query strictly ascending ids (all below 1 000 000); query q gets counts[(q + shift) % counts.size()] of them
+static void filter_batch(uint64_t nq, const std::vector<uint32_t> &counts, size_t shift, std::mt19937_64 &rng,
+                         std::vector<uint64_t> *off, std::vector<uint64_t> *ids) {
+  off->assign(nq + 1, 0), ids->clear();
+  for (uint64_t q = 0; q < nq; q++) {
+    uint64_t id = 1 + rng() % 50;
+    for (uint32_t i = 0; i < counts[(q + shift) % counts.size()]; i++, id += 1 + rng() % 4) ids->push_back(id);
+    (*off)[q + 1] = ids->size();
+  }
+}
+
+static void test_filter_host_matches_model() {
+  std::mt19937_64 rng(20251019);
+  std::vector<uint64_t> off, ids;
+  size_t sorted_queries = 0;
+  for (uint32_t search_size : {5u, 75u}) {
+    const std::vector<uint32_t> counts = {0, 1, search_size - 1, search_size, search_size + 1, 1000};
+    for (uint64_t nq : {1, 7, 64})
+      for (unsigned nthr : {1u, 3u, 16u})  // (16 threads and 1 or 7 queries: more threads than queries)
+        for (bool reused : {false, true})
+          for (size_t shift = 0; shift < counts.size(); shift++) {
+            filter_batch(nq, counts, shift, rng, &off, &ids);
+            const auto slot_of = [reused](uint64_t id) { return filter_slot_of(id, reused); };
+            std::vector<uint32_t> off_seed, off_filt;
+            uint64_t bad_q = 0;
+            const sdb::FilterHostError err = sdb::filter_host_count(nq, off.data(), ids.data(), search_size, nthr, slot_of,
+                                                                    off_seed, off_filt, &bad_q);
+            CHECK(err == sdb::kFilterHostOk, "valid lists, error %d", (int)err);
+            if (err != sdb::kFilterHostOk || off_seed.size() != nq + 1 || off_filt.size() != nq + 1) {
+              CHECK(err != sdb::kFilterHostOk, "offset arrays of %zu and %zu entries for %" PRIu64 " queries", off_seed.size(),
+                    off_filt.size(), nq);
+              continue;
+            }
+            std::vector<uint32_t> seeds(off_seed[nq] + 1, 0xDEADBEEFu), fslots(off_filt[nq] + 1, 0xDEADBEEFu);
+            sdb::filter_host_fill(nq, off.data(), ids.data(), search_size, nthr, slot_of, off_seed, off_filt, seeds.data(),
+                                  fslots.data());
+            CHECK(seeds.back() == 0xDEADBEEFu && fslots.back() == 0xDEADBEEFu, "a write past the lists");
+            for (uint64_t q = 0; q < nq; q++) {  // the model: resolve, drop the unknown, first searchSize positions, sort
+              std::vector<uint32_t> m_seeds, m_slots;
+              for (uint64_t i = off[q]; i < off[q + 1]; i++) {
+                const int64_t s = filter_slot_of(ids[i], reused);
+                if (s < 0) continue;
+                if (i - off[q] < search_size) m_seeds.push_back((uint32_t)s);
+                m_slots.push_back((uint32_t)s);
+              }
+              sorted_queries += !std::is_sorted(m_slots.begin(), m_slots.end());
+              std::sort(m_slots.begin(), m_slots.end());
+              const std::vector<uint32_t> g_seeds(seeds.begin() + off_seed[q], seeds.begin() + off_seed[q + 1]);
+              const std::vector<uint32_t> g_slots(fslots.begin() + off_filt[q], fslots.begin() + off_filt[q + 1]);
+              CHECK(g_seeds == m_seeds, "seeds of query %" PRIu64 " of %" PRIu64 " (%u threads, searchSize %u, %zu ids)", q, nq,
+                    nthr, search_size, (size_t)(off[q + 1] - off[q]));
+              CHECK(g_slots == m_slots, "slots of query %" PRIu64 " of %" PRIu64 " (%u threads, searchSize %u, %zu ids)", q, nq,
+                    nthr, search_size, (size_t)(off[q + 1] - off[q]));
+            }
+          }
+  }
+  CHECK(sorted_queries > 100, "only %zu queries needed the sort", sorted_queries);
+}
+
+// exactly one offending query per batch, so the query reported is that one
+static void test_filter_host_errors() {
+  std::mt19937_64 rng(7);
+  const auto slot_of = [](uint64_t id) { return filter_slot_of(id, false); };
+  for (uint64_t nq : {1, 7, 64})
+    for (unsigned nthr : {1u, 3u, 16u}) {
+      // one array of ids ascending throughout, 20 per query: whatever window a query's offsets name is a valid list
+      std::vector<uint64_t> off(nq + 1), ids(20 * nq + 20);
+      for (size_t i = 0; i < ids.size(); i++) ids[i] = 2 + 3 * i;
+      for (uint64_t q = 0; q <= nq; q++) off[q] = 20 * q;
+      const uint64_t at = rng() % nq;
+      std::vector<uint32_t> off_seed, off_filt;
+      uint64_t bad_q = ~0ull;
+      std::vector<uint64_t> dec = off;
+      dec[at + 1] = dec[at] - (at ? 5 : 0), dec[at] += at ? 0 : 5;  // offsets[at + 1] < offsets[at], every other step upwards
+      CHECK(sdb::filter_host_count(nq, dec.data(), ids.data(), 5, nthr, slot_of, off_seed, off_filt, &bad_q) ==
+                sdb::kFilterOffsetsDecrease, "offsets that decrease at query %" PRIu64 " of %" PRIu64 " (%u threads)", at, nq, nthr);
+      std::vector<uint64_t> dup = ids;
+      dup[off[at] + 11] = dup[off[at] + 10];  // not STRICTLY ascending, in the middle of query `at`
+      bad_q = ~0ull;
+      CHECK(sdb::filter_host_count(nq, off.data(), dup.data(), 5, nthr, slot_of, off_seed, off_filt, &bad_q) ==
+                sdb::kFilterIdsNotAscending && bad_q == at,
+            "a repeated id in query %" PRIu64 " of %" PRIu64 " (%u threads): reported %" PRIu64, at, nq, nthr, bad_q);
+      dup = ids;
+      dup[off[at] + 19] = dup[off[at] + 3];  // a descent at the query's last id
+      bad_q = ~0ull;
+      CHECK(sdb::filter_host_count(nq, off.data(), dup.data(), 75, nthr, slot_of, off_seed, off_filt, &bad_q) ==
+                sdb::kFilterIdsNotAscending && bad_q == at,
+            "a descent in query %" PRIu64 " of %" PRIu64 " (%u threads): reported %" PRIu64, at, nq, nthr, bad_q);
+    }
+}
+
 // not part of the suite: proves that the sanitizer of this build is awake (tests/test_host_concurrency.py runs it by
 // name and demands a report): an unsynchronised counter and a read past a heap block
 static int g_racy = 0;
@@ -733,6 +835,8 @@ int main(int argc, char **argv) {
       {"exchange_order", test_exchange_order},
       {"exchange_missing_rank", test_exchange_missing_rank},
       {"vamana_readers_and_writers", test_vamana_readers_and_writers},
+      {"filter_host_matches_model", test_filter_host_matches_model},
+      {"filter_host_errors", test_filter_host_errors},
   };
   int ran = 0;
   if (argc > 1 && std::string(argv[1]) == "seeded_bugs") {

@@ -302,6 +302,14 @@ def test_filters_as_bitmaps_give_the_same_walk(oracle, dense):
     l_ids, l_d, l_c, ltr = ix.search_batch(q, k, L, filters=filters, trace=True, visit_cap=1024)
     assert np.array_equal(g_ids, l_ids) and np.array_equal(bits(g_d), bits(l_d)) and np.array_equal(g_c, l_c)
     assert np.array_equal(tr.visit_ids, ltr.visit_ids) and np.array_equal(tr.n_dist, ltr.n_dist)
+    # the same bitmaps with the host's translation asked for (tuning host_filters): they become id lists inside the call
+    ix.set_tuning("host_filters", 1)
+    try:
+        h_ids, h_d, h_c, htr = ix.search_batch(q, k, L, filters=bm, trace=True, visit_cap=1024)
+    finally:
+        ix.set_tuning("host_filters", 0)
+    assert np.array_equal(h_ids, l_ids) and np.array_equal(bits(h_d), bits(l_d)) and np.array_equal(h_c, l_c)
+    assert np.array_equal(htr.visit_ids, ltr.visit_ids) and np.array_equal(htr.n_dist, ltr.n_dist)
     for i in range(nq):
         o_ids, o_d, o_vis, o_tr = o.search(q[i], k, L, filter_ids=sorted(filters[i]))
         assert int(g_c[i]) == len(o_ids), i

@@ -4,10 +4,12 @@ The reference's contract for the hot path is concurrency: one goroutine per requ
 shard's RLock (shard/index/search.go:53-87, shard/cache/manager.go:159-181), ClusterNode.SearchPoints fans a request out
 to every shard at once (cluster/actions.go:316-351), and its own suite runs under Go's race detector
 (.vscode/tasks.json:7).  The drop-in's equivalents -- the lock-free SearchBatcher, IndexVamana / GpuFanout
-(semadb_amd/host/semadb_host.hpp) and the ticket turnstile / ring slots / group rendezvous of the shard exchange
-(semadb_amd/csrc/turnstile.h, the very code cluster.hip compiles) -- are driven here by tests/host/test_concurrency.cpp
-against a CPU stand-in of the C ABI (tests/host/mock_sdb.cpp) that answers every query with a function of the query, so
-each answer is checked against the request that asked for it.
+(semadb_amd/host/semadb_host.hpp), the ticket turnstile / ring slots / group rendezvous of the shard exchange
+(semadb_amd/csrc/turnstile.h, the very code cluster.hip compiles) and the threaded translation of a batch's filter ids
+to slot lists (semadb_amd/csrc/filter_host.h, the very code search_batch.hip compiles) -- are driven here by
+tests/host/test_concurrency.cpp against a CPU stand-in of the C ABI (tests/host/mock_sdb.cpp) that answers every query
+with a function of the query, so each answer is checked against the request that asked for it; the filter translation
+is checked against a single-threaded model of it.
 
 clang's runtimes are used (the image's g++ 11 libtsan does not know pthread_cond_clockwait, which libstdc++'s
 condition_variable::wait_for calls, and reports every timed wait as a double lock)."""
@@ -61,7 +63,8 @@ def test_host_concurrency_under_sanitizer(kind, tmp_path):
     for name in ("batcher_mixed", "batcher_backpressure", "batcher_window_race", "batcher_pageable",
                  "batcher_poll_and_reissue", "batcher_destructor", "turnstile_order", "turnstile_missing_ticket",
                  "view_mutex_writer_gets_its_turn",
-                 "fanout", "exchange_order", "exchange_missing_rank", "vamana_readers_and_writers"):
+                 "fanout", "exchange_order", "exchange_missing_rank", "vamana_readers_and_writers",
+                 "filter_host_matches_model", "filter_host_errors"):
         assert "ok   " + name in out.stdout, tail
 
 
@@ -69,6 +72,16 @@ def test_index_uses_the_tested_view_lock():
     src = open(os.path.join(ROOT, "semadb_amd", "csrc", "index.h")).read()
     assert '#include "view_mutex.h"' in src and "class ViewMutex" not in src
     assert "mutable sdb::ViewMutex view_mu;" in src
+
+
+def test_search_call_uses_the_tested_filter_translation():
+    """search_batch.hip must run the two passes the cases drive, not a copy of them"""
+    src = open(os.path.join(ROOT, "semadb_amd", "csrc", "search_batch.hip")).read()
+    assert '#include "filter_host.h"' in src
+    for used in ("filter_host_count(", "filter_host_fill("):
+        assert used in src, used
+    for gone in ("std::thread>", "pool.emplace_back", "std::sort("):
+        assert gone not in src, "search_batch.hip grew its own copy of the host translation: " + gone
 
 
 def test_cluster_source_uses_the_tested_turnstile():
