@@ -16,7 +16,8 @@
 
 #include "bq.h"
 #include "pq.h"
-#include "search_kernel.h"
+#include "walk_plan.h"
+#include "wave_dist.h"
 
 #ifndef SDB_DCACHE_BITS
 #define SDB_DCACHE_BITS 13
@@ -1553,8 +1554,9 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     if (bq)
       sa.bq_codes = reinterpret_cast<const uint64_t *>(ix->d_codes), sa.bq_thr = bq->d_thr, sa.bq_W = bq->W,
       sa.bq_metric = (uint32_t)bq->metric;
-    if (!search_uses_hash(sa, rs)) SDB_W_HIP(hipMemsetAsync(bitsets, 0, (size_t)rs * words * 4, stream));
-    SDB_W_TRY(launch_greedy_search(sa, rs, stream));  // read-only on the graph: a failure here adds nothing to what the rounds before it did
+    const WalkPlan plan = plan_walk(sa, rs);
+    if (plan.clear_bitsets) SDB_W_HIP(hipMemsetAsync(bitsets, 0, (size_t)rs * words * 4, stream));
+    SDB_W_TRY(launch_walk_plan(plan, sa, rs, stream));  // read-only on the graph: a failure here adds nothing to what the rounds before it did
     // ---- robustPrune + back-edges
     BuildArgs ba{};
     ba.slab = ix->d_slab, ba.adj = ix->d_adj, ba.deg = ix->d_deg, ba.clean = ix->d_clean;

@@ -8,7 +8,8 @@
 #include <cfloat>
 
 #include "bq.h"
-#include "search_kernel.h"
+#include "index.h"
+#include "wave_dist.h"
 
 namespace sdb {
 

@@ -23,7 +23,7 @@
 
 #include "bq.h"
 #include "pq.h"
-#include "search_kernel.h"
+#include "wave_dist.h"
 
 namespace sdb {
 

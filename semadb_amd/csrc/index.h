@@ -88,12 +88,14 @@ struct RerankArgs {
   uint32_t rerank = 0, limit = 0;
   int metric = 0;
 };
-constexpr uint32_t kRerankMax = 512;  // searchSize's ceiling on the device (launch_greedy_search)
+constexpr uint32_t kRerankMax = 512;  // searchSize's ceiling on the device (walk_plan.h plan_walk)
 int launch_rerank(const RerankArgs &a, uint32_t nq, hipStream_t stream);
 
-// index.hip, for the search call (search_batch.hip; launch_greedy_search and search_uses_hash: search_kernel.h)
+// walk_launch.hip: launches the kernel that plan_walk() (walk_plan.h) chose for the call (search_batch.hip, build.hip)
 struct SearchArgs;
-bool sketch_walk(const SearchArgs &a, uint32_t nq);  // the call takes the two-precision hop's kernel (its visited set needs no clearing ahead)
+struct WalkPlan;
+int launch_walk_plan(const WalkPlan &plan, const SearchArgs &a, uint32_t nq, hipStream_t stream);
+int launch_greedy_search(const SearchArgs &a, uint32_t nq, hipStream_t stream);  // plan, then launch, for a call whose bitsets are zero already: nothing here clears them
 // the device's address of page-locked host memory the kernels can read and write in place; false: pageable, or not mapped
 bool device_view_of_host(const void *p, size_t bytes, void **dev);
 
@@ -217,7 +219,7 @@ struct sdb_index {
   bool tune_host_filters = false;  // filter ids are resolved to slots by the host's hash map even when the table's ids are consecutive
   uint32_t tune_wide_walk = 0;  // the workgroup-per-query walk of small calls: 0 = up to 256 queries, 1 = never, 2 = always
   bool tune_no_zero_copy = false;  // A/B and parity tests: host-memory searches stage even page-locked buffers
-  // Two-precision hop (SDB_TUNE_SKETCH; search_kernel.h SearchArgs::sketch): a float16 copy of the slab's rows, an
+  // Two-precision hop (SDB_TUNE_SKETCH; walk_args.h SearchArgs::sketch): a float16 copy of the slab's rows, an
   // optional cache like d_adjcodes.  It describes the rows of the view published as number `sketch_gen`; a search
   // uses it only while that is the current view.  Every path that publishes rows (load, commit, publish_full,
   // rollback, compact) brings it up to date behind the searches of the old view, and reserve() carries it across
@@ -242,7 +244,7 @@ struct sdb_index {
   // and within-margin neighbours (4 d each) stay below the float16 stage's 2.86 d, i.e. while kept + within-margin stays
   // below 0.41 of the evaluated; DESIGN 4 records the replay that turns that share into this ratio.
   static constexpr float kSketch8MaxRatio = 0.16f;
-  bool sketch8_supported() const;  // sketch_supported() and search_kernel.h stage_int8(): cosine / dot, rows of up to 384 floats
+  bool sketch8_supported() const;  // sketch_supported() and walk_args.h stage_int8(): cosine / dot, rows of up to 384 floats
   bool sketch8_wanted() const { return tune_sketch >= 3 && !tune_sketch_filtered && !sketch8_refused && sketch8_supported(); }  // (SDB_TUNE_SKETCH_FILTERED: the filtered hop reads the float16 copy)
   size_t sketch_row_bytes(bool int8) const { return int8 ? (size_t)lay.ld : (size_t)lay.ld * 2; }
   void *d_sketch = nullptr;  // rows of ld halves, or (sketch8) of ld bytes
@@ -252,7 +254,7 @@ struct sdb_index {
   float sk_emax = 0.0f, sk_ymax = 0.0f;
   unsigned long long *d_sk_counters = nullptr;  // [0] neighbours discarded on their float16 distance, [1] contradicted (audit)
   std::mutex sketch_mu;  // held by build_sketch on the commit path (view_mu released) and by the knob: lock order sketch_mu, view_mu
-  // plain rows of whole 32-float blocks in one of the walk's register layouts (search_kernel.h stage_shape()), any metric, no quantizer
+  // plain rows of whole 32-float blocks in one of the walk's register layouts (walk_args.h stage_shape()), any metric, no quantizer
   bool sketch_supported() const;
   bool sketch_current() const { return d_sketch && sketch_gen == view_gen; }  // describes the current view's rows
   static bool sketch_room(size_t bytes);  // the device keeps max(4 GB, total / 16) free after `bytes` more (a cache's rule, build.hip pairc)

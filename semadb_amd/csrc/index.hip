@@ -1,5 +1,5 @@
-// index.hip -- K3 (HBM slab + adjacency loader), the index's host-side state and K2's launcher (launch_greedy_search); the
-// search call itself is search_batch.hip.
+// index.hip -- K3 (HBM slab + adjacency loader) and the index's host-side state; the search call itself is
+// search_batch.hip, the walk's launcher walk_launch.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -9,7 +9,8 @@
 
 #include "bq.h"
 #include "pq.h"
-#include "search_kernel.h"
+#include "walk_args.h"
+#include "wave_dist.h"
 
 namespace sdb {
 
@@ -171,275 +172,6 @@ __global__ void k_idmap_build(const uint64_t *__restrict__ ids, uint32_t n, uint
 __global__ void k_fill_u32(uint32_t *p, uint32_t v, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
-}
-
-// ------------------------------------------------------------------------------------------
-// search launcher
-// ------------------------------------------------------------------------------------------
-// LDS hash visited set: plain store with the query in registers, unfiltered, reference-range search size.
-// Any batch size: four resident waves per CU already saturate the memory system with this kernel, and a long
-// batch keeps them resident back to back (batch 16 384: 1.18 M QPS, 7.3 TB/s, against 0.88 M QPS on the
-// bitset variant at 16 waves per CU).
-// the multi-wave quantized walk (search_kernel.h PQWideDist): which instantiation serves (M, K), or -1
-static int pq_wide_shape(const SearchArgs &a) {
-  if (!a.pq_codes || a.pq_narrow == 1 || a.filt_off || a.prefer_bitset) return -1;
-  if (a.search_size > 96 || a.pq_K > 256 || a.pq_K % 32) return -1;
-  switch (a.pq_M) {
-    case 128: return 1;  // NL 15, RT 17 (two queries per CU)
-    case 192: return 2;  // NL 15, RT 33 (two queries per CU)
-    case 256: return 3;  // NL 32, RT 32
-    case 384: return 4;  // NL 15, RT 33, eight waves
-    default: return -1;  // M <= 64: the table fits beside a one-wave walk
-  }
-}
-
-// SPLIT (the candidate array in a helper wave, search_kernel.h pqw_split_walker): plain searches on a start node
-// without an overflow list; SDB_TUNE_PQ_NARROW = 3 keeps the walker-does-everything form for comparison
-template <int NL, int RT, int W, int NLW, bool SPLIT>
-static int launch_pqw_form(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  const bool h16 = (uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash;
-  const size_t lut = (size_t)((W - 1) * NL + NLW) * a.pq_K * sizeof(float);
-  static std::atomic<uint64_t> at16{0}, at32{0};
-  if (h16) {
-    const size_t lds = HashVisited16::kWords * 4 + sizeof(PQWideShared) + lut;
-    if (first_use_on_this_device(at16))
-      SDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_greedy_search_pqw<NL, RT, kHash16, W, NLW, SPLIT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    hipLaunchKernelGGL((k_greedy_search_pqw<NL, RT, kHash16, W, NLW, SPLIT>), dim3(nq), dim3(64 * W), lds, stream, a);
-  } else {
-    const size_t lds = HashVisited<kHashCapPQ>::kWords * 4 + sizeof(PQWideShared) + lut;
-    if (first_use_on_this_device(at32))
-      SDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_greedy_search_pqw<NL, RT, kHashCapPQ, W, NLW, SPLIT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    hipLaunchKernelGGL((k_greedy_search_pqw<NL, RT, kHashCapPQ, W, NLW, SPLIT>), dim3(nq), dim3(64 * W), lds, stream, a);
-  }
-  SDB_HIP(hipGetLastError());
-  return SDB_OK;
-}
-template <int NL, int RT, int W = 4, int NLW = NL>
-static int launch_pqw(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  if constexpr (W == 4 && NL == 15)  // M = 128 / 192, two queries per CU (M = 192 at 2M x 768: 1.050 -> 0.989 ms per batch)
-    if (a.pq_narrow != 3 && !a.vis_slots && !a.dcache && !a.start_ext_n) return launch_pqw_form<NL, RT, W, NLW, true>(a, nq, stream);
-  return launch_pqw_form<NL, RT, W, NLW, false>(a, nq, stream);
-}
-
-bool search_uses_hash(const SearchArgs &a, uint32_t nq) {
-  // filtered searches too (round 3): their search set takes the same table, their result set a 4 KB one beside it
-  // (search_kernel.h kHashCapResult) -- no 2 x 128 MB bitset clear per batch, no HBM atomic per edge
-  if (a.prefer_bitset) return false;
-  if (a.search_size > 96) return false;
-  // quantized store: only with the small LUT of M*K <= 2048 entries next to the table (M = 32's 32 KB LUT leaves
-  // room for three walks per CU beside the 16 KB table: 0.95 M QPS against 1.31 M on the bitset at five)
-  if (a.pq_codes) return pq_wide_shape(a) >= 0 || (a.pq_lut_in_lds && (size_t)a.pq_M * a.pq_K <= 2048);
-  if (a.bq_codes) return true;  // bit codes: the query is 512 bytes of LDS beside the table
-  switch (a.ng) {
-    case 0: case 1: case 2: case 3: case 4: case 6: case 8: case 12: case 16: case 24: return true;
-    default: return false;
-  }
-}
-
-// The quantized walk with its table in LDS, on two waves per query (search_kernel.h k_greedy_search_pq2: the walker and
-// the merger): plain unfiltered searches of the reference's searchSize range; a build's searches (visit log), a start
-// node with an overflow list and SDB_TUNE_PQ_NARROW = 1 keep the one-wave kernel.
-static bool pq_two_waves(const SearchArgs &a, uint32_t nq) {
-  if (!a.pq_codes || !a.pq_lut_in_lds || (size_t)a.pq_M * a.pq_K > 2048 || a.pq_narrow == 1) return false;
-  if (a.filt_off || a.vis_slots || a.dcache || a.start_ext_n || a.search_size > 96) return false;
-  return search_uses_hash(a, nq);
-}
-template <uint32_t HCAP>
-static int launch_pq2(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  constexpr uint32_t vis = HCAP == kHash16 ? HashVisited16::kWords : HashVisited<HCAP == kHash16 ? 4u : HCAP>::kWords;
-  const size_t lds = ((size_t)vis + (((size_t)a.pq_M * a.pq_K + 3) & ~(size_t)3) + kPq2SharedWords) * sizeof(uint32_t);
-  hipLaunchKernelGGL((k_greedy_search_pq2<HCAP>), dim3(nq), dim3(128), lds, stream, a);
-  SDB_HIP(hipGetLastError());
-  return SDB_OK;
-}
-
-// HCAP: 0 = bitset, else the LDS hash set's capacity (it precedes the policy's own LDS of `lds` bytes)
-template <class Dist, uint32_t HCAP>
-static int launch_nreg(const SearchArgs &a, uint32_t nq, hipStream_t stream, size_t lds) {
-  const bool filt = a.filt_off != nullptr;
-  const size_t rwords = filt ? HashVisited<kHashCapResult>::kWords * sizeof(uint32_t) : 0;
-  if constexpr (HCAP == kHash16) {
-    const size_t total = HashVisited16::kWords * sizeof(uint32_t) + rwords + lds;
-    if (filt) hipLaunchKernelGGL((k_greedy_search<Dist, 2, true, HCAP>), dim3(nq), dim3(64), total, stream, a);
-    else hipLaunchKernelGGL((k_greedy_search<Dist, 2, false, HCAP>), dim3(nq), dim3(64), total, stream, a);
-  } else if constexpr (HCAP != 0) {
-    const size_t total = HashVisited<HCAP>::kWords * sizeof(uint32_t) + rwords + lds;
-    if (filt) hipLaunchKernelGGL((k_greedy_search<Dist, 2, true, HCAP>), dim3(nq), dim3(64), total, stream, a);
-    else hipLaunchKernelGGL((k_greedy_search<Dist, 2, false, HCAP>), dim3(nq), dim3(64), total, stream, a);
-  } else if (a.search_size <= 128) {
-    if (filt) hipLaunchKernelGGL((k_greedy_search<Dist, 2, true, 0>), dim3(nq), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((k_greedy_search<Dist, 2, false, 0>), dim3(nq), dim3(64), lds, stream, a);
-  } else {
-    if (filt) hipLaunchKernelGGL((k_greedy_search<Dist, 8, true, 0>), dim3(nq), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((k_greedy_search<Dist, 8, false, 0>), dim3(nq), dim3(64), lds, stream, a);
-  }
-  SDB_HIP(hipGetLastError());
-  return SDB_OK;
-}
-
-// The workgroup-per-query walk (search_kernel.h PlainWideDist) for calls with few queries: a 256-query call is one
-// workgroup per CU.  Waves per workgroup, measured at 1M x 384 (tools/bench_latency.py, whole call of 1 / 256 queries;
-// one wave per query: 0.538 / 0.598 ms): 2 waves 0.78 / 0.86, 4 waves 0.536 / 0.607, 8 waves 0.410 / 0.469, 16 waves
-// 0.361 / 0.416 ms -- a hop's ~50 rows are 2 pairs per wave then, one short burst of loads each.  With the helpers
-// pulling the likely next hop's rows through L2 (PlainWideDist::pull_ahead): 0.336 / 0.419 ms; 0.371 at 128 queries
-// (0.408 without); with the helpers COMPUTING that hop's distances ahead (compute_ahead): 0.316 / 0.405 ms, 0.362 at 128.
-// Past 256 queries eight waves per query (0.58 ms at 512 against 0.66 for one wave per query, 0.80 for sixteen).  Plain store, query in registers; the build's warm-up rounds (up to 512 points) included.
-constexpr uint32_t kWideMaxQueries = 256;
-#ifndef SDB_WIDE_AHEAD
-#define SDB_WIDE_AHEAD 256
-#endif
-constexpr uint32_t kWideAheadQueries = SDB_WIDE_AHEAD;
-#ifndef SDB_WIDE_WAVES
-#define SDB_WIDE_WAVES 16
-#endif
-constexpr int kWideWaves = SDB_WIDE_WAVES;
-static bool wide_walk(const SearchArgs &a, uint32_t nq) {
-  // (the build's warm-up rounds come here too -- rounds of up to 512 points while the graph is small, ~330 of a 1M
-  // build's ~580 rounds: their visit logs and distance tables are written by the walker like any other wave's)
-  if (a.wide_mode == 1 || a.pq_codes || a.bq_codes || !search_uses_hash(a, nq)) return false;
-  // 257 .. 512 queries (eight waves per query): faster than one wave per query for rows of up to 384 floats only
-  // (d = 384: 0.56 against 0.65 ms; 512: 0.98 against 0.78; 768: 1.20 against 1.05; profiles/r05_latency.json)
-  return a.wide_mode == 2 || nq <= (a.ng <= 3 ? 2 : 1) * kWideMaxQueries;
-}
-template <int NG, bool L2, int W>
-static int launch_wide_w(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  using D = PlainWideDist<NG, L2, W>;
-  const size_t lds = HashVisited<kHashCap>::kWords * sizeof(uint32_t) + D::kLdsBytes;
-  SearchArgs b = a;
-  // calls of up to 256 queries (a workgroup per CU at most): the other waves work ahead on the row the walk expands next
-  b.wide_pull = ((W == 16 || NG == 8) && nq <= kWideAheadQueries) ? 2u : 0u;
-  if (a.filt_off)  // the filtered walk (search.go:33-51,93-95): a hybrid REST query is one query with a filter
-    hipLaunchKernelGGL((k_greedy_search_wide<NG, L2, W, true>), dim3(nq), dim3(64 * W),
-                       lds + HashVisited<kHashCapResult>::kWords * sizeof(uint32_t), stream, b);
-  else
-    hipLaunchKernelGGL((k_greedy_search_wide<NG, L2, W, false>), dim3(nq), dim3(64 * W), lds, stream, b);
-  SDB_HIP(hipGetLastError());
-  return SDB_OK;
-}
-// up to 256 queries: 16 waves per query (one workgroup per CU); up to 512: 8 waves (two per CU: 0.56 ms per call against
-// 0.66 for one wave per query and 0.78 for 16 waves)
-// rows of 1 024 floats: at sixteen waves (128 registers each) the query and two pairs of rows do not fit -- 17 .. 57
-// registers spilled -- so every small call of that shape takes the eight-wave workgroup (214 registers, none spilled)
-template <int NG, bool L2>
-static int launch_wide(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  if constexpr (NG != 8)
-    if (nq <= kWideMaxQueries || kWideWaves != 16) return launch_wide_w<NG, L2, kWideWaves>(a, nq, stream);
-  return launch_wide_w<NG, L2, 8>(a, nq, stream);
-}
-
-// The two-precision hop's kernel (SearchArgs::sketch): batch walks, plain and -- where the caller of launch_greedy_search
-// handed the copy to a filtered call (SDB_TUNE_SKETCH_FILTERED) -- filtered searches.  A filtered call keeps the hop up to
-// searchSize 128 (the two array registers of the kernel), also at 97 .. 128, where search_uses_hash() sends plain calls
-// to the bitset kernel: the LDS sets spill to the query's bitsets by themselves (HashVisited::spill clears the bitset
-// first), so such a call needs no bitset cleared ahead either (sketch_walk() is asked by the launcher and by the clear).
-bool sketch_walk(const SearchArgs &a, uint32_t nq) {
-  if (a.stage == Stage::kNone || a.pq_codes || a.bq_codes || a.vis_slots || a.dcache || a.tail != 0 || a.search_size > 128) return false;
-  if (!stage_shape((int)a.ng)) return false;
-  if (wide_walk(a, nq)) return false;
-  return search_uses_hash(a, nq) || (a.filt_off && !a.prefer_bitset);
-}
-
-template <int NG, bool L2>
-static int launch_plain(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  if constexpr (NG >= 1 && NG <= 8)
-    if (wide_walk(a, nq)) return launch_wide<NG, L2>(a, nq, stream);
-  const bool hash = search_uses_hash(a, nq);
-  if constexpr (stage_shape(NG))
-    if (sketch_walk(a, nq)) {
-      // (few float32 rows survive the first stage: four pairs of them in flight per round leave the registers to the copy's rows)
-      if constexpr (stage_int8(NG, L2, false))
-        if (a.stage == Stage::kInt8) {  // the int8 first stage (SDB_TUNE_SKETCH = 3, 4): plain calls of cosine / dot tables
-          using Sk8Dist = Int8Dist<NG>;
-          hipLaunchKernelGGL((k_greedy_search<Sk8Dist, 2, false, kHashCap>), dim3(nq), dim3(64),
-                             HashVisited<kHashCap>::kWords * sizeof(uint32_t) + Sk8Dist::kLdsBytes, stream, a);
-          SDB_HIP(hipGetLastError());
-          return SDB_OK;
-        }
-      using SkDist = PlainDist<NG, L2, true, 4, Stage::kHalf>;
-      const size_t lds = HashVisited<kHashCap>::kWords * sizeof(uint32_t) + SkDist::kLdsBytes;
-      if (a.filt_off)  // all three filter forms; the threshold is search_kernel.h list_tail_bound
-        hipLaunchKernelGGL((k_greedy_search<SkDist, 2, true, kHashCap>), dim3(nq), dim3(64),
-                           lds + HashVisited<kHashCapResult>::kWords * sizeof(uint32_t), stream, a);
-      else
-        hipLaunchKernelGGL((k_greedy_search<SkDist, 2, false, kHashCap>), dim3(nq), dim3(64), lds, stream, a);
-      SDB_HIP(hipGetLastError());
-      return SDB_OK;
-    }
-  if (hash) return launch_nreg<PlainDist<NG, L2, true>, kHashCap>(a, nq, stream, PlainDist<NG, L2, true>::kLdsBytes);
-  return launch_nreg<PlainDist<NG, L2, false>, 0>(a, nq, stream, PlainDist<NG, L2, false>::kLdsBytes);
-}
-
-template <bool L2>
-static int launch_ng(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  const size_t lds = (size_t)(a.ng * 128 + 32) * sizeof(float);
-  switch (a.ng) {
-    case 0: return launch_plain<0, L2>(a, nq, stream);
-    case 1: return launch_plain<1, L2>(a, nq, stream);
-    case 2: return launch_plain<2, L2>(a, nq, stream);
-    case 3: return launch_plain<3, L2>(a, nq, stream);
-    case 4: return launch_plain<4, L2>(a, nq, stream);
-    case 6: return launch_plain<6, L2>(a, nq, stream);
-    case 8: return launch_plain<8, L2>(a, nq, stream);
-    case 12: return launch_plain<12, L2>(a, nq, stream);  // 1536
-    case 16: return launch_plain<16, L2>(a, nq, stream);  // 2048
-    case 24: return launch_plain<24, L2>(a, nq, stream);  // 3072
-    default: return launch_nreg<PlainDist<-1, L2>, false>(a, nq, stream, lds);
-  }
-}
-
-// Bit codes (search_kernel.h BitDist): the one-wave walk with every visited-set policy the product one-wave walk has --
-// the 16-bit-cell LDS set for tables of up to 2^24 rows, the 32-bit-cell one beyond, the HBM bitset (SDB_TUNE_NO_HASH,
-// searchSize > 96) -- plain and filtered.  No multi-wave, two-precision or small-call variant.
-template <bool JACCARD>
-static int launch_bits(const SearchArgs &a, uint32_t nq, hipStream_t stream) {
-  using D = BitDist<JACCARD>;
-  if (search_uses_hash(a, nq)) {
-    if ((uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash) return launch_nreg<D, kHash16>(a, nq, stream, D::kLdsBytes);
-    return launch_nreg<D, kHashCapPQ>(a, nq, stream, D::kLdsBytes);
-  }
-  return launch_nreg<D, 0>(a, nq, stream, D::kLdsBytes);
-}
-
-int launch_greedy_search(const SearchArgs &a_in, uint32_t nq, hipStream_t stream) {
-  if (nq == 0) return SDB_OK;
-  SearchArgs a = a_in;
-  if (a.hash_limit == 0 || a.hash_limit > kHashLimit) a.hash_limit = kHashLimit;
-  if (a.search_size == 0 || a.search_size > 512)
-    return fail(SDB_ERR_INVALID, "searchSize %u not supported on device (1..512)", a.search_size);
-  if (a.bq_codes) {  // binary quantizer with a threshold attached (binary.go:191-200)
-    if (a.bq_metric == SDB_METRIC_JACCARD) return launch_bits<true>(a, nq, stream);
-    return launch_bits<false>(a, nq, stream);
-  }
-  if (a.pq_codes) {  // fitted product quantizer attached (product.go:250-277)
-    switch (pq_wide_shape(a)) {  // tables too large to sit beside a one-wave walk: one query per four waves
-      case 1: return a.pq_narrow == 2 ? launch_pqw<32, 0>(a, nq, stream) : launch_pqw<15, 17>(a, nq, stream);  // two per CU
-      // M = 192: 15 tables per wave in LDS and 33 in registers leave room for TWO queries per CU (643 k against
-      // 570 k QPS at 10M x 768 with 32 + 16, one query per CU: profiles/r03_c4_10Mx768_pq.log); SDB_TUNE_PQ_NARROW = 2
-      // selects the latter for comparison
-      case 2: return a.pq_narrow == 2 ? launch_pqw<32, 16>(a, nq, stream) : launch_pqw<15, 33>(a, nq, stream);
-      case 3: return launch_pqw<32, 32>(a, nq, stream);
-      // M = 384: eight waves with M = 192's per-wave layout, the walker 24 + 24 (129 tables in LDS: with the 32-bit-cell
-      // visited set 162 064 of the 162 816 bytes a workgroup may ask for)
-      case 4: return launch_pqw<15, 33, 8, 24>(a, nq, stream);
-      default: break;
-    }
-    const size_t lds = a.pq_lut_in_lds ? (size_t)a.pq_M * a.pq_K * sizeof(float) : 0;
-    if (pq_two_waves(a, nq)) {
-      if ((uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash) return launch_pq2<kHash16>(a, nq, stream);
-      return launch_pq2<kHashCapPQ>(a, nq, stream);
-    }
-    if (search_uses_hash(a, nq)) {
-      // up to 2^24 rows: the 16-bit-cell set (16 KB, six walks per CU); beyond: 32-bit cells
-      if ((uint64_t)a.words_per_query * 32 <= (1u << 24) && !a.wide_hash)
-        return a.pq_lut_in_lds ? launch_nreg<PQLdsDist, kHash16>(a, nq, stream, lds) : launch_nreg<PQGlobalDist, kHash16>(a, nq, stream, lds);
-      return a.pq_lut_in_lds ? launch_nreg<PQLdsDist, kHashCapPQ>(a, nq, stream, lds) : launch_nreg<PQGlobalDist, kHashCapPQ>(a, nq, stream, lds);
-    }
-    return a.pq_lut_in_lds ? launch_nreg<PQLdsDist, 0>(a, nq, stream, lds) : launch_nreg<PQGlobalDist, 0>(a, nq, stream, lds);
-  }
-  if (a.metric == SDB_METRIC_EUCLIDEAN) return launch_ng<true>(a, nq, stream);
-  return launch_ng<false>(a, nq, stream);
 }
 
 }  // namespace sdb

@@ -12,7 +12,7 @@
 #include <cfloat>
 
 #include "index.h"
-#include "search_kernel.h"
+#include "wave_dist.h"
 
 namespace sdb {
 

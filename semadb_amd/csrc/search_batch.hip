@@ -1,6 +1,6 @@
 // search_batch.hip -- the host side of K2: one batch search call from its arguments to the launch (the four
-// sdb_index_search_batch* entry points), and the kernels that turn a call's filter into slot lists.  The launcher
-// (launch_greedy_search and its dispatch) is index.hip's.
+// sdb_index_search_batch* entry points), and the kernels that turn a call's filter into slot lists.  Which
+// kernel walks is walk_plan.h's decision; walk_launch.hip launches it.
 #include <algorithm>
 #include <memory>
 #include <new>
@@ -10,7 +10,7 @@
 #include "bq.h"
 #include "filter_host.h"
 #include "pq.h"
-#include "search_kernel.h"
+#include "walk_plan.h"
 
 namespace sdb {
 
@@ -619,9 +619,9 @@ static int attach_quantizer(const sdb_index *ix, Workspace *ws, uint64_t nq, hip
 static int launch_walk(sdb_index *ix, Workspace *ws, SearchArgs &a, RerankPlan *rp, uint64_t nq, size_t bitset_bytes, bool tail,
                        hipStream_t stream) {
   SDB_TRY(attach_quantizer(ix, ws, nq, stream, a));
+  const WalkPlan plan = plan_walk(a, (uint32_t)nq);
   // ClearAll (distset.go:101); the LDS hash variant clears a bitset only for a query that overflows it
-  if (!search_uses_hash(a, (uint32_t)nq) && !sketch_walk(a, (uint32_t)nq))
-    SDB_HIP(hipMemsetAsync(ws->bitsets.p, 0, bitset_bytes, stream));
+  if (plan.clear_bitsets) SDB_HIP(hipMemsetAsync(ws->bitsets.p, 0, bitset_bytes, stream));
   RerankArgs *ra = rp ? &rp->ra : nullptr;
   if (ra) {  // the walk's outputs go to the workspace; what the caller (or the staging) named is k_rerank's to write
     ra->queries = a.queries, ra->out_ids = a.out_ids, ra->out_dists = a.out_dists, ra->out_counts = a.out_counts;
@@ -630,7 +630,7 @@ static int launch_walk(sdb_index *ix, Workspace *ws, SearchArgs &a, RerankPlan *
   const bool prof = ix->profiling && !ix->ev0.empty();
   const uint32_t slot = (uint32_t)(ix->prof_count % sdb_index::kProfRing);
   if (prof) (void)hipEventRecord(ix->ev0[slot], stream);
-  int rc = launch_greedy_search(a, (uint32_t)nq, stream);
+  int rc = launch_walk_plan(plan, a, (uint32_t)nq, stream);
   if (prof) {
     (void)hipEventRecord(ix->ev1[slot], stream);
     ix->prof_count++;

@@ -19,111 +19,12 @@
 //     through a rank-compacted LDS list, a row address is one 64-bit mad (PlainDist::hop_fast).
 #pragma once
 #include "bq.h"
-#include "dist_core.h"
 #include "index.h"
+#include "walk_args.h"
+#include "wave_dist.h"
 #include <type_traits>
 
 namespace sdb {
-
-// The two-precision hop's first stage: which copy of the rows a walk reads first (SearchArgs::sketch), if any.
-enum class Stage : uint32_t { kNone = 0, kHalf = 1, kInt8 = 2 };
-// Which tables and calls get which stage -- stated here once, for the launcher, the index and the kernels alike.
-// A stage at all: the group counts whose float16 rounds fit the walk's registers.
-constexpr bool stage_shape(int ng) { return ng == 1 || ng == 2 || ng == 3 || ng == 4 || ng == 6; }
-// Rows asked for ahead: rows of up to 384 floats, where all 64 edges' copy rows fit the register file.
-constexpr bool stage_ahead(int ng) { return stage_shape(ng) && ng <= 3; }
-// The int8 stage: those tables, cosine / dot, plain calls (a filtered call reads the float16 copy or none).
-constexpr bool stage_int8(int ng, bool euclidean, bool filtered) { return stage_ahead(ng) && !euclidean && !filtered; }
-
-struct SearchArgs {
-  const float *slab;
-  const uint32_t *adj;
-  const uint64_t *ids;
-  uint32_t *bitsets;
-  uint32_t words_per_query;
-  const float *queries;  // [nq][dim] original layout
-  uint32_t dim, nblk, ng, tail, ld;
-  uint32_t start_slot;
-  // the start node's edges beyond its 64-entry row (index.h h_start_ext), kNoSlot-padded to whole chunks of 64
-  const uint32_t *start_ext;
-  uint32_t start_ext_n;
-  uint32_t search_size;
-  uint32_t limit;
-  int metric;
-  uint64_t *out_ids;
-  float *out_dists;
-  uint32_t *out_counts;
-  uint32_t *tr_ndist, *tr_nhop, *tr_nedges;
-  uint64_t *tr_visit;
-  uint32_t visit_cap;
-  // build path: the visit log as (slot, dist), in visit order
-  uint32_t *vis_slots;
-  float *vis_dists;
-  uint32_t *vis_count;
-  uint32_t vis_cap;
-  // product-quantized store (product.go:238-277): per-query LUT [nq][M*K] and per-slot codes [n][M]
-  const float *pq_lut;
-  const uint8_t *pq_codes;
-  uint32_t pq_M, pq_K;
-  // != NULL: the code rows of every node's neighbours behind its adjacency row, [rows][64][M] (index.h d_adjcodes), for
-  // the copy of the graph `adj` points at
-  const uint8_t *adj_codes;
-  uint32_t adj_rows;  // rows of `adj` (what tells an adjacency row from a chunk of the start node's overflow list)
-  uint32_t pq_lut_in_lds;  // != 0: the kernel copies its LUT into LDS first
-  uint32_t pq_narrow;      // 1: never a multi-wave walk (k_greedy_search_pqw, k_greedy_search_pq2); 2: the one-query-per-CU variant of the former for M = 192
-
-  // filtered search (search.go:33-51,93-95): per query CSR of seeds (<= searchSize slots, ascending id
-  // order) and of the whole filter as ascending slots; rbitsets = the result set's own visited set
-  const uint32_t *seed_off, *seeds, *filt_off, *filt_slots;
-  // filter lists resolved on the device (search_batch.hip k_filter_resolve): the counts are not offset differences then
-  // (segments keep the caller's offsets, unknown ids leave gaps at their ends); NULL: offset differences
-  const uint32_t *seed_cnt, *filt_cnt;
-  // != NULL: Contains (:93) is answered from the filter's IDS -- the uploaded lists, strictly ascending, at filt_off's
-  // offsets -- with the id of the expanded node (ids[slot]), for tables where ascending ids are not ascending slots
-  // (an id that was deleted and inserted again sits behind larger ids); filt_slots is not read then
-  const uint64_t *filt_ids;
-  uint32_t *rbitsets;
-  // build path, full-precision store: every evaluated (slot, distance) also goes into the query's
-  // direct-mapped table of 2^(32 - dcache_shift) entries (last writer wins); the back-edge prunes of the
-  // round look their pair distances up there (build.hip BuildArgs::dcache).  NULL: not collected.
-  uint2 *dcache;
-  uint32_t dcache_shift;
-  unsigned long long *totals;  // build path: [0] += n_dist, [1] += n_edges of every query (sdb_index_build_stats)
-  uint32_t prefer_bitset;  // != 0: never use the LDS hash visited set (large build rounds)
-  uint32_t wide_hash;      // != 0: quantized store keeps the 32-bit-cell set (HashVisited) instead of HashVisited16
-  uint32_t hash16_probes;  // test knob: buckets a key of HashVisited16 may try (0 = all 15); fewer make the `stuck` spill common
-  uint32_t hash_limit;     // ids the LDS hash set may hold before the query falls back to its bitset
-  uint32_t wide_mode;      // the workgroup-per-query walk: 0 = calls of up to kWideMaxQueries queries, 1 = never, 2 = always
-  uint32_t wide_pull;      // 2: that walk's other waves work ahead on the row the walk expands next (PlainWideDist); 0: they only share a hop's rows
-  // Two-precision hop (index.h d_sketch; SDB_TUNE_SKETCH): a float16 copy of the slab, same element order, rows of
-  // `ld` halves.  A neighbour whose float16 distance lies above the candidate array's last distance by more than the
-  // bound on |float16 distance - the reference's float32 distance| is discarded by AddWithLimit whatever its exact
-  // distance is (distset.go:184; the distance is never looked at again), so only the others are read in float32.
-  const void *sketch;                // Stage::kHalf: rows of `ld` halves; Stage::kInt8: rows of `ld` bytes
-  const float *sketch_norm;          // [rows] ||y16||^2 of every row (euclidean tables: d16 = ||q16||^2 + ||y16||^2 - 2 q16.y16)
-  float sk_emax, sk_ymax;            // max over the rows of ||y - y16|| and of ||y16|| (k_sketch_rows), rounded up; the int8 copy's likewise
-  Stage stage;                       // this call's first stage, decided once where the arguments are filled (search_batch.hip choose_stage); kNone: `sketch` is NULL
-  float sk8_scale;                   // the int8 copy's scale s: y8 = clamp(rint(y / s), -127, 127)
-  uint32_t sk_audit;                 // != 0: evaluate everything exactly as well and count decisions the exact distance contradicts
-  unsigned long long *sk_counters;   // [0] += neighbours discarded on their float16 distance, [1] += contradicted ones (audit)
-  // binary-quantized store (binary.go:187-200): per-slot codes [n][W] of 64-bit words, the threshold [dim] the walk
-  // encodes its query with, and the bit metric (SDB_METRIC_HAMMING / SDB_METRIC_JACCARD); bq_codes == NULL: none
-  const uint64_t *bq_codes;
-  const float *bq_thr;
-  uint32_t bq_W, bq_metric;
-};
-
-// pairs of candidate rows a wave keeps in flight per chunk.  DEEP (one wave per SIMD, the batch-search
-// configuration: 4 waves per CU, the whole 512-entry register file available): ~190 VGPRs of loads;
-// otherwise ~96 so that three waves per SIMD still fit (large build rounds).
-template <int NG, bool DEEP>
-struct ChunkPairs {
-  static constexpr int base = NG <= 3 ? 8 : NG <= 4 ? 6 : NG <= 6 ? 4 : NG <= 8 ? 3 : NG <= 12 ? 2 : 1;
-#ifndef SDB_DEEP3_PAIRS
-#define SDB_DEEP3_PAIRS 16  // measurement builds: pairs per round of the d = 384 batch walk (tools/kernel_ab.py)
-#endif
-  static constexpr int value = DEEP ? (NG == 3 ? SDB_DEEP3_PAIRS : 2 * base) : base;  // DEEP: 32 / 24 / 16 / 12 / 8 / 4 rows in flight
-};
 
 // The kernel's own arguments once more, through a pointer the optimiser cannot see through.  Every walk kernel takes
 // its SearchArgs by value as its first parameter, i.e. at offset 0 of the kernarg segment; a field read through `a` is
@@ -140,125 +41,6 @@ __device__ __forceinline__ ColdArgs &cold_args(const SearchArgs &) {
   asm volatile("" : "+s"(p));
   return *(ColdArgs *)p;
 }
-template <class T>
-__device__ __forceinline__ __attribute__((address_space(1))) T *as_global(T *p) {
-  return (__attribute__((address_space(1))) T *)p;
-}
-// 1, 2 or 3 dwords of device memory at a 4-byte-aligned address, one load instruction
-typedef uint32_t gwords2 __attribute__((ext_vector_type(2), aligned(4)));
-typedef uint32_t gwords3 __attribute__((ext_vector_type(3), aligned(4)));
-typedef const __attribute__((address_space(1))) char *gbytes;  // a byte address in device memory
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ float rlf(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// Ordering point for LDS traffic inside ONE wavefront (the search kernels run one wave per workgroup): the
-// LDS queue is in order per wave, so a ds_write is visible to the wave's later ds_reads without a barrier;
-// only the compiler has to keep the order (and nothing waits for outstanding global loads, as a
-// __syncthreads() would).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// U pairs of (query, candidate) raw distances; slot[u] is this lane's candidate row (same for the
-// 32 lanes of a half).  res[u] is valid in lanes 0 and 32.
-template <int NG, bool L2, int U>
-__device__ __forceinline__ void chunk_dist(const float *__restrict__ slab, uint32_t ld, uint32_t tail,
-                                           const float4 (&xq)[NG > 0 ? NG : 1], float xt,
-                                           const uint32_t (&slot)[U], float (&res)[U], int lane
-#ifdef SDB_STAMPS
-                                           , unsigned long long *st = nullptr
-#endif
-) {
-  const int L = lane & 31;
-  float4 y[U][NG > 0 ? NG : 1];
-  float yt[U];
-#ifdef SDB_STAMPS
-  unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    const float *row = slab + (size_t)slot[u] * ld;
-    const float4 *r4 = reinterpret_cast<const float4 *>(row) + L;
-#pragma unroll
-    for (int g = 0; g < NG; g++) y[u][g] = r4[g * 32];
-    yt[u] = tail ? row[NG * 128 + L] : 0.0f;
-  }
-#ifdef SDB_STAMPS
-  unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  unsigned long long t2 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int g = 0; g < NG; g++) acc = chain4<L2>(acc, xq[g], y[u][g]);
-    float t = tail ? tail_chain<L2>(xt, yt[u], tail, lane) : 0.0f;
-    res[u] = asm_reduce(acc, t, lane);
-  }
-#ifdef SDB_STAMPS
-  asm volatile("" ::"v"(res[U - 1]));
-  unsigned long long t3 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (st) st[0] += t1 - t0, st[1] += t2 - t1, st[2] += t3 - t2;  // issue, wait, compute
-#endif
-}
-
-// Generic-dimension variant: the permuted query tile lives in LDS (qs, ng*32 float4 + 32 tail floats).
-template <bool L2, int U>
-__device__ __forceinline__ void chunk_dist_lds(const float *__restrict__ slab, uint32_t ld, uint32_t ng,
-                                               uint32_t tail, const float *qs, const uint32_t (&slot)[U],
-                                               float (&res)[U], int lane) {
-  const int L = lane & 31;
-  float acc[U];
-  const float4 *r4[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    acc[u] = 0.0f;
-    r4[u] = reinterpret_cast<const float4 *>(slab + (size_t)slot[u] * ld) + L;
-  }
-  const float4 *q4 = reinterpret_cast<const float4 *>(qs) + L;
-  // four 128-float groups of every row per step: 4 * U row loads in flight instead of U; the partial sums
-  // still take their groups in ascending order
-  constexpr int GC = 4;
-  for (uint32_t g0 = 0; g0 < ng; g0 += GC) {
-    float4 y[U][GC];
-#pragma unroll
-    for (int k = 0; k < GC; k++)
-      if (g0 + k < ng) {
-#pragma unroll
-        for (int u = 0; u < U; u++) y[u][k] = r4[u][(g0 + k) * 32];
-      }
-#pragma unroll
-    for (int k = 0; k < GC; k++)
-      if (g0 + k < ng) {
-        const float4 x = q4[(g0 + k) * 32];
-#pragma unroll
-        for (int u = 0; u < U; u++) acc[u] = chain4<L2>(acc[u], x, y[u][k]);
-      }
-  }
-  float xt = tail ? qs[ng * 128 + L] : 0.0f;
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    float yt = tail ? slab[(size_t)slot[u] * ld + ng * 128 + L] : 0.0f;
-    float t = tail ? tail_chain<L2>(xt, yt, tail, lane) : 0.0f;
-    res[u] = asm_reduce(acc[u], t, lane);
-  }
-}
-
-typedef _Float16 sk_h2 __attribute__((ext_vector_type(2)));
-// float -> float16 as the sketch stores it: round to nearest, magnitudes below the smallest NORMAL half become 0 (no
-// denormal half is ever an operand of v_dot2_f32_f16, whatever the mode register says about them); what this loses is
-// part of the measured error ||v - v16||, not an assumption
-__device__ __forceinline__ _Float16 sk_half(float v) { return fabsf(v) < 6.103515625e-5f ? (_Float16)0.0f : (_Float16)v; }
 
 // ---- the two-precision hop's first stage (SearchArgs::sketch, SDB_TUNE_SKETCH): one implementation (FirstStage) over
 // two formats of the copy.  A format says how the query is converted and its error measured, how one copy row is
@@ -526,7 +308,7 @@ struct FirstStage {
   }
 
   // A hop asks for its copy rows ahead; `loaded` says whether keep() may use them (the array is full).  The walk is
-  // launched only with the copy (index.hip launch_plain), so the pointer need not be tested -- and untested, the compiler
+  // launched only with the copy (walk_plan.h: the staged families), so the pointer need not be tested -- and untested, the compiler
   // sees that keep()'s compacting path is never taken with the rows asked for ahead: 87 -> 14 spilled SGPRs at NG = 3
   // (cosine / dot).  The euclidean walk keeps the test (through the opaque view) in front of its loads: untested, this
   // compiler spills 4 VGPRs there; tested, none.
@@ -1646,45 +1428,7 @@ struct PQWideDist {
 
 // ---- the candidate array (DistSet.items, distset.go:133-138) held in registers -------------------------
 // entry e lives in lane e % 64 of register e / 64; bit 31 of the slot word is the `visited` flag.
-
-// bubble position + shift of DistSet.AddWithLimit (distset.go:189-198) for one accepted point
-template <int NREG>
-__device__ __forceinline__ void list_insert(uint32_t (&cid)[NREG], float (&cd)[NREG], int &len, int cap, uint32_t id,
-                                            float d, int lane) {
-  const bool full = (len == cap);
-  const int newlen = full ? len : len + 1;  // :189-194 append, or overwrite the tail
-  const int range = newlen - 1;             // entries the bubble loop compares against
-  int pos = 0;                              // :196-198 stops at the first i with !(d < items[i-1])
-#pragma unroll
-  for (int r = 0; r < NREG; r++) {
-    uint64_t m = __ballot((r * 64 + lane) < range && !(d < cd[r]));
-    if (m) pos = r * 64 + 64 - __clzll(m);
-  }
-#pragma unroll
-  for (int r = NREG - 1; r >= 0; r--) {
-    // entry e-1 -> e: one v_mov_b32_dpp wave_shr:1 per register; lane 0 takes the carry (lane 63 of the
-    // previous register) through the DPP `old` operand
-    uint32_t c_id = 0;
-    float c_d = 0.0f;
-    if (r > 0) c_id = rl(cid[r - 1], 63), c_d = rlf(cd[r - 1], 63);
-    const uint32_t up_id = (uint32_t)__builtin_amdgcn_update_dpp((int)c_id, (int)cid[r], 0x138, 0xf, 0xf, false);
-    const float up_d =
-        __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(c_d), __float_as_int(cd[r]), 0x138, 0xf, 0xf, false));
-    const int e = r * 64 + lane;
-    if (e > pos && e < newlen) cid[r] = up_id, cd[r] = up_d;
-    else if (e == pos) cid[r] = id, cd[r] = d;
-  }
-  len = newlen;
-}
-
-template <int NREG>
-__device__ __forceinline__ float list_tail(const float (&cd)[NREG], int cap) {
-  float t = 0.0f;
-#pragma unroll
-  for (int r = 0; r < NREG; r++)
-    if (((cap - 1) >> 6) == r) t = rlf(cd[r], (cap - 1) & 63);
-  return t;
-}
+// (list_insert and list_tail, which the flat scan shares: wave_dist.h)
 
 // The filtered walk's array is NOT sorted (its seeds are appended by Add, distset.go:203-211, and AddWithLimit bubbles a
 // point left only while it is `<` its neighbour, :193-198), so its last distance can RISE while a chunk's points are
@@ -1882,7 +1626,7 @@ struct BitVisited {
 // bitset, replays every stored key into it and carries on there -- the set stays exact and the walk is
 // not repeated (the reference makes the same kind of switch by id range, distset.go:140-153).
 constexpr uint32_t kHashCap = 8192;    // plain store: 32 KB per wave -> 4 waves per CU
-constexpr uint32_t kHashLimit = 6000;  // keys a table may hold before it spills (any CAP: limit * CAP / 8192)
+// (kHashLimit, the keys a table may hold before it spills -- any CAP: limit * CAP / 8192 -- is walk_args.h's)
 constexpr uint32_t kHashCapPQ = 7417;  // quantized store: a prime, 29 KB, leaves room for the 8 KB LUT (M = 8)
 #ifndef SDB_HASH_PROBES
 #define SDB_HASH_PROBES 4  // 6 and 8 measured the same (tools/kernel_ab.py: 0.947 / 0.947 / 0.946 ms plain, 0.315 / 0.312 / 0.317 ms quantized)
@@ -2882,7 +2626,7 @@ __device__ __forceinline__ void pq2_merger(const SearchArgs &a, const uint32_t q
 }
 
 // Dynamic LDS: [visited set's table][the query's M x K table][Pq2Shared].  Unfiltered searches with searchSize <= 128,
-// no visit log for a build, no overflow list on the start node (index.hip launch_greedy_search decides).
+// no visit log for a build, no overflow list on the start node (walk_plan.h decides).
 // (A workgroup of four waves with the walker on wave (blockIdx / 256) % 4 and the merger two SIMDs on -- the placement
 // trick of k_greedy_search_pqw -- was slower: 0.370 against 0.323 ms at 4M x 768.)
 template <uint32_t HCAP>
@@ -3078,11 +2822,5 @@ __global__ __launch_bounds__(64 * W) void k_greedy_search_wide(const SearchArgs 
   }
   dist.finish(lane);
 }
-
-// host-side launcher: picks the instantiation for (ng, metric, search_size)
-int launch_greedy_search(const SearchArgs &a, uint32_t nq, hipStream_t stream);
-
-// true when launch_greedy_search will use the LDS hash visited set (then the bitsets need no clearing)
-bool search_uses_hash(const SearchArgs &a, uint32_t nq);
 
 }  // namespace sdb

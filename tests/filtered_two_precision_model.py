@@ -270,7 +270,7 @@ def width_case(orc, metric, d, full_rows, limit=10, L=40):
 
 
 # (L, limit); L = 40 is the width cases'.  1 and 2: min(k, L) is the whole array; 96 / 97: the last searchSize with the
-# LDS hash set by routing and the first without (index.hip search_uses_hash) -- a filtered call keeps the hop on both sides
+# LDS hash set by routing and the first without (csrc/walk_plan.h) -- a filtered call keeps the hop on both sides
 L_CASES = ((1, 1), (2, 1), (5, 5), (10, 10), (64, 10), (96, 10), (97, 10), (128, 10))
 L_NO_STAGE = 129                 # past the kernel's two array registers: the float32 walk
 L_REFUSED = (5, 10)              # searchSize < limit: refused by both sides (search.go:23-25)

@@ -17,7 +17,7 @@ All cases run with wide_walk = 1 (one wave per query, the kernel that has the st
 with the opt-in SDB_TUNE_SKETCH_FILTERED set: without it (the default) a filtered call reads float32 rows only
 (test_off_by_default).
 
-The routing these tests state (index.hip sketch_walk, not imported): a filtered call takes the stage at every batch
+The routing these tests state (csrc/walk_plan.h, not imported): a filtered call takes the stage at every batch
 size when searchSize is 97 .. 128 (the many-waves kernel needs the LDS hash set, which ends at 96), at searchSize <= 96
 when the many-waves kernel does not keep the call (wide_walk = 1, or more than 512 / 256 queries), never with
 no_hash = 1, never inside an open transaction, never past searchSize 128.
@@ -116,7 +116,7 @@ def test_widths_metrics_and_filter_sizes(oracle, metric, d, full_rows):
 
 @pytest.mark.parametrize("metric", F.METRICS)
 def test_search_sizes(oracle, metric):
-    """L = 1 and 2 (min(k, L) is the whole array), 5 = limit, 10, 64, 96 / 97 (either side of search_uses_hash: a
+    """L = 1 and 2 (min(k, L) is the whole array), 5 = limit, 10, 64, 96 / 97 (either side of the plain calls' LDS set, csrc/walk_plan.h: a
     filtered call keeps the hop, and from 97 on no bitset is cleared ahead of the launch), 128 (the last the kernel's two
     array registers hold); L < limit: refused; L = 129: the float32 walk"""
     first = F.width_case(oracle, metric, 128, False)
@@ -249,7 +249,7 @@ def test_default_dispatch_beyond_the_hash_set(oracle):
     """searchSize 100, wide_walk at its default: the many-waves kernel is out of the dispatch at every batch size, so
     calls of 8, 64 and 513 queries all take the stage -- each inside its own sandwich with lower > 0, the same per-query
     answers from the three.  Once more with LDS sets that give up after 24 ids: they spill into bitsets that nobody
-    cleared ahead of the launch (sketch_walk() makes the launcher skip the clear)."""
+    cleared ahead of the launch (csrc/walk_plan.h: the plan of such a call asks for no clear)."""
     case = F.dispatch_beyond_hash_case(oracle)
     reps, _ = case.model(oracle)
     _oracle_equals_replay(F.Case(case.what, case.metric, case.d, case.ex, case.o, case.queries[:64], case.filters[:64],

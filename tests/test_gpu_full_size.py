@@ -186,7 +186,7 @@ def test_c2_oracle_walks_the_same_path(c2, oracle):
         assert np.array_equal(g_ids[i], o_ids) and np.array_equal(bits(g_d[i]), bits(o_d))
         assert int(tr.n_dist[i]) == o_tr.n_dist and int(tr.n_hop[i]) == o_tr.n_hop
         assert np.array_equal(vis[i, :o_tr.n_hop], o_vis), "query %d visit order" % i
-    # A call of 96 queries runs on the many-waves-per-query kernel (index.hip wide_walk()).  The same queries on the
+    # A call of 96 queries runs on the many-waves-per-query kernel (csrc/walk_plan.h).  The same queries on the
     # one-wave-per-query walk, the kernel every large batch takes, with its two-precision hop over full rows (R = 64):
     discarded = c2.ix.sketch_stats()[0]
     c2.ix.set_tuning("wide_walk", 1)

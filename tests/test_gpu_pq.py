@@ -564,7 +564,7 @@ def test_two_wave_walk_names_what_the_array_says(metric, d, M, K):
     vs.attach(ix, pq)
     q = base[rng.choice(n, 512, replace=False)] + 0.05 * rng.standard_normal((512, d)).astype(np.float32)
     # (the two-wave kernel serves tables of up to 2 048 entries on graphs whose start node has no overflow list --
-    # index.hip pq_two_waves; rocprofv3 --kernel-trace of this test shows k_greedy_search_pq2 beside k_greedy_search<PQDist>)
+    # csrc/walk_plan.h; rocprofv3 --kernel-trace of this test shows k_greedy_search_pq2 beside k_greedy_search<PQDist>)
     assert M * K <= 2048
     _, _, g_off, _ = ix.export(with_vectors=False)
     assert int(g_off[1] - g_off[0]) <= 64

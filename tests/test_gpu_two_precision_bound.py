@@ -31,7 +31,7 @@ from tests.helpers import bits, unit_rows
 
 pytestmark = pytest.mark.gpu
 
-# index.hip wide_walk(): with the default dispatch a plain call of up to 512 queries (rows of up to 384 floats) or up
+# csrc/walk_plan.h: with the default dispatch a plain call of up to 512 queries (rows of up to 384 floats) or up
 # to 256 queries (wider rows) runs on the many-waves-per-query kernel, which has no first stage; above, one wave per
 # query walks, with the stage.  Stated here, not imported.
 WIDE_UP_TO = {128: 512, 512: 256}
@@ -166,7 +166,7 @@ def test_search_sizes_limits_and_hostile_queries(oracle, metric, d):
             continue
         _sandwich(ix, oracle, o, g, metric, queries, limit, L, what, expect="some")
     for L in M.L_BEYOND:
-        # Present routing: searchSize > 96 leaves the hash set (index.hip search_uses_hash) and with it the kernel that
+        # Present routing: searchSize > 96 leaves the hash set (csrc/walk_plan.h) and with it the kernel that
         # has the stage, so nothing is discarded.  Should a later change let the stage run there, the sandwich applies.
         what = "%s d=%d L=%d" % (metric, d, L)
         reps, t, _ = M.run_model(oracle, g, metric, queries, 10, L)

@@ -309,7 +309,7 @@ def width_case(orc, metric, d):
 
 
 L_CASES = ((1, 1), (2, 1), (5, 1), (10, 1), (64, 1), (96, 1), (1, 10), (2, 10), (5, 10), (10, 10), (64, 10), (96, 10))
-L_BEYOND = (97, 128)  # the stage is behind search_uses_hash (searchSize <= 96): present routing discards nothing there
+L_BEYOND = (97, 128)  # the stage is behind the LDS visited set (csrc/walk_plan.h: searchSize <= 96): present routing discards nothing there
 
 
 def l_case(orc, metric, d):

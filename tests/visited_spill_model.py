@@ -147,7 +147,7 @@ WIDE8_QUERIES = 300               # 257 .. 512 queries: eight waves per query an
 WIDE8_CHECKED = 32                # compared with the oracle one by one; the rest with the T = 0 run
 WIDE8_CASES = [("cosine", 128), ("cosine", 384)]
 FILTERED_QUERIES = 24
-SEAM = (512, 513)                 # index.hip wide_walk(): 512 queries stay on the many-waves kernel at d = 128
+SEAM = (512, 513)                 # csrc/walk_plan.h: 512 queries stay on the many-waves kernel at d = 128
 
 
 @functools.lru_cache(maxsize=None)
