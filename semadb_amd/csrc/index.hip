@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void k_sketch_rows(const float *__restrict__ s
   }
 }
 
-// ---- the int8 copy (SDB_TUNE_SKETCH = 3, 4; search_kernel.h Int8Rows) ----
+// ---- the int8 copy (SDB_TUNE_SKETCH = 3, 4; walk_stage.h Int8Rows) ----
 // the largest |element| of `count` floats into *out (a NaN's pattern is above every number's)
 __global__ __launch_bounds__(256) void k_sketch8_absmax(const float *__restrict__ v, size_t count, uint32_t *__restrict__ out) {
   uint32_t m = 0;

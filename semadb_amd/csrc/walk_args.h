@@ -102,11 +102,11 @@ struct SearchArgs {
   uint32_t bq_W, bq_metric;
 };
 
-// keys an LDS visited set may hold before it spills to the query's bitset (search_kernel.h HashVisited; any CAP:
+// keys an LDS visited set may hold before it spills to the query's bitset (visited_set.h HashVisited; any CAP:
 // limit * CAP / 8192)
 constexpr uint32_t kHashLimit = 6000;
 
-// The workgroup-per-query walk (search_kernel.h PlainWideDist) for calls with few queries: a 256-query call is one
+// The workgroup-per-query walk (walk_dist_rows.h PlainWideDist) for calls with few queries: a 256-query call is one
 // workgroup per CU.  Waves per workgroup, measured at 1M x 384 (tools/bench_latency.py, whole call of 1 / 256 queries;
 // one wave per query: 0.538 / 0.598 ms): 2 waves 0.78 / 0.86, 4 waves 0.536 / 0.607, 8 waves 0.410 / 0.469, 16 waves
 // 0.361 / 0.416 ms -- a hop's ~50 rows are 2 pairs per wave then, one short burst of loads each.  With the helpers

@@ -25,13 +25,9 @@ static int no_kernel(const WalkPlan &p) {
   return fail(SDB_ERR_STATE, "no walk kernel for plan (family %u, visited %u, ng %d, waves %d)", (unsigned)p.family, (unsigned)p.visited, p.ng, p.waves);
 }
 
-// HCAP: 0 = bitset, kHash16 = HashVisited16, else HashVisited<HCAP>; the set precedes the policy's own LDS
+// the visited set HCAP names (visited_set.h VisitedFor) precedes the policy's own LDS
 template <uint32_t HCAP>
-constexpr size_t set_bytes() {
-  if constexpr (HCAP == 0) return 0;
-  else if constexpr (HCAP == kHash16) return HashVisited16::kWords * sizeof(uint32_t);
-  else return HashVisited<HCAP>::kWords * sizeof(uint32_t);
-}
+constexpr size_t set_bytes() { return VisitedFor<HCAP>::kWords * sizeof(uint32_t); }
 constexpr size_t kResultSetBytes = set_bytes<kHashCapResult>();  // a filtered walk's result set, beside an LDS set
 
 // k_greedy_search, one wave per query; dist_lds: the distance policy's own LDS

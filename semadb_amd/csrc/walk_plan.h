@@ -37,7 +37,7 @@ inline WalkPlan plan_walk(const SearchArgs &a, uint32_t nq) {
   p.nreg = a.search_size <= 128 ? 2 : 8;
   p.l2 = a.metric == SDB_METRIC_EUCLIDEAN;
   // An LDS visited set at all: the reference's searchSize range, filtered searches too (their result set takes a 4 KB
-  // table beside it, search_kernel.h kHashCapResult) -- no bitset clear per batch, no HBM atomic per edge.
+  // table beside it, visited_set.h kHashCapResult) -- no bitset clear per batch, no HBM atomic per edge.
   const bool small = a.search_size <= 96 && !a.prefer_bitset;
   // The set beside a code table: 16-bit cells (16 KB, six walks per CU) for up to 2^24 rows, 32-bit cells beyond.
   const WalkVisited beside_codes =

@@ -5,7 +5,7 @@ sorted and its last distance can RISE while a chunk of neighbours is inserted: A
 and bubbles it left only while it is `<` its neighbour (:193-198), and the new last entry is then the old second-to-last
 one.  The plain walk's rule -- discard what is provably above the last distance as the chunk starts -- is wrong here.
 
-The rule the kernel uses (search_kernel.h list_tail_bound): with the array full as a chunk starts and k new neighbours
+The rule the kernel uses (cand_array.h list_tail_bound): with the array full as a chunk starts and k new neighbours
 in the chunk, B = the maximum of the array's last min(k, L) distances; a neighbour whose reference distance is above B
 is discarded at its turn whatever happens before it.  (One kept insertion puts x <= tail somewhere and shifts what is
 behind it right by one, so the tail after j insertions is at most the maximum of the original last j + 1 entries, and

@@ -8,7 +8,7 @@ kernel's arithmetic.  The walk, the replay and the tally are tests/two_precision
   q^ = (s_q / 128)(128 a + b), in the kernel's float32 steps;
 * the exact integer sum W = sum (128 a + b) y8 and d8 = metric(s (s_q / 128) W), exact in float64;
 * the bound: upper  d8 - (||q - q^|| Y8max + ||q|| E8max) > tail,
-             lower  the same with every inflation the kernel documents (search_kernel.h Int8Rows) charged generously.
+             lower  the same with every inflation the kernel documents (walk_stage.h Int8Rows) charged generously.
 
 The kernel's derivation implies  lower <= discarded on the device <= upper <= discardable.
 """

@@ -2,7 +2,7 @@
 
 A filtered walk's candidate array is not sorted (its seeds are appended by Add), so its last distance can rise within
 a chunk of neighbours; the kernel's threshold is B, the maximum of the array's last min(k, L) distances as a chunk with
-k new neighbours starts (search_kernel.h list_tail_bound).  tests/filtered_two_precision_model.py restates the filtered
+k new neighbours starts (cand_array.h list_tail_bound).  tests/filtered_two_precision_model.py restates the filtered
 walk in numpy and counts, against B, the neighbours the pure float16 bound proves discardable (`upper`) and those it
 still proves with every inflation the kernel documents charged generously (`lower`).  For sketch = 2 (audit) and then 1
 every case asserts the oracle's answers per query (ids, distance bits, counts, n_dist / n_hop / n_edges, visit order),

@@ -413,7 +413,7 @@ def test_quantized_walk_is_the_same_under_every_visited_set(oracle):
 def test_multi_wave_quantized_walk_parity(oracle, metric, d, M, K):
     """Round 3: a quantizer whose per-query table does not fit beside a one-wave walk (M = 128 .. 384) is searched by
     four waves per query -- tables in LDS and in registers, the waves adding their index ranges in turn
-    (search_kernel.h PQWideDist).  Ids, LUT-distance bits, visit order and counters equal the oracle's, equal the one-wave
+    (walk_dist_codes.h PQWideDist).  Ids, LUT-distance bits, visit order and counters equal the oracle's, equal the one-wave
     kernel's (table in global memory, SDB_TUNE_PQ_NARROW), and stay equal when the visited set spills or is a bitset."""
     from semadb_amd import vamana, vectorstore as vs
     rng = np.random.default_rng(d + M + K)
@@ -454,6 +454,65 @@ def test_multi_wave_quantized_walk_parity(oracle, metric, d, M, K):
         got = ix.search_batch(q, 10, 50, trace=True, visit_cap=512)
         assert np.array_equal(got[0], g_ids) and np.array_equal(bits(got[1]), bits(g_d)), key
         assert np.array_equal(got[3].n_dist, tr.n_dist) and np.array_equal(got[3].visit_ids, tr.visit_ids), key
+    ix.close()
+    gpq.close()
+
+
+@pytest.mark.parametrize("d,M,narrows", [(128, 128, (0, 3, 1)), (96, 8, (0, 1))])
+def test_result_rows_into_dirty_buffers(oracle, d, M, narrows):
+    """The result copy (cand_array.h write_results) from every caller it has among the quantized walks, straight into
+    the caller's device tensors, which hold a sentinel.  60 rows walked with limit = searchSize = 64: a walk returns at
+    most 59 ids, so every row has a tail, which the kernel has to fill with zeros.  M = 128 (SDB_TUNE_PQ_NARROW 0, 3,
+    1): the split multi-wave walk's merger, its walker's own search_body, the one-wave kernel; M = 8 (0, 1): the
+    two-wave walk's merger, the one-wave kernel.  Ids, distance bits and counts are the oracle's, the start node is
+    absent, and the trace is the same under every setting of one index."""
+    import torch
+    from semadb_amd import vamana, vectorstore as vs
+    rng = np.random.default_rng(d + M)
+    n, K, R, L, nq, limit = 60, 32, 16, 32, 8, 64
+    o = build_oracle_index(oracle, unit_rows(rng, n, d), "cosine", R=R, L=L)
+    ids, vecs, off, edges = o.export()
+    train = vecs[1:n + 1].copy()
+    first = rng.integers(0, n, M)
+    opq = oracle.PQ(d, "cosine", M, K)
+    opq.fit(train.copy(), first, alias=True)
+    assert o.attach_pq(opq, np.stack([opq.encode(v) for v in vecs])) == 0
+    q = unit_rows(rng, nq, d)
+    want = [o.search(q[k], limit, limit) for k in range(nq)]
+    start_id = int(ids[0])
+    for o_ids, _, _, _ in want:  # from the oracle alone: every row has a tail, and no row holds the start node
+        assert len(o_ids) < limit and start_id not in [int(v) for v in o_ids]
+    ix = vamana.NewIndexVamana("dirty", vamana.IndexVectorVamanaParameters(d, "cosine", L, R, 1.2), strict=False)
+    ix.load(ids, vecs, off, edges)
+    gpq = vs.ProductQuantizer("cosine", vs.ProductQuantizerParameters(K, M), d)
+    gpq.Fit(train.copy(), first, alias=True)
+    vs.attach(ix, gpq)
+    q_dev = torch.from_numpy(q).cuda()
+    traces = []
+    for narrow in narrows:
+        ix.set_tuning("pq_narrow", narrow)
+        out = (torch.full((nq, limit), 0xA5A5A5A5A5A5A5A5 - (1 << 64), dtype=torch.int64, device="cuda"),
+               torch.full((nq, limit), float("nan"), dtype=torch.float32, device="cuda"),
+               torch.full((nq,), -1, dtype=torch.int32, device="cuda"))  # 0xFFFFFFFF
+        g_ids, g_d, g_c, tr = ix.search_batch(q_dev, limit, limit, trace=True, visit_cap=128, out=out)
+        torch.cuda.synchronize()
+        assert g_ids.data_ptr() == out[0].data_ptr() and g_d.data_ptr() == out[1].data_ptr() and g_c.data_ptr() == out[2].data_ptr()
+        g_ids, g_d, g_c = g_ids.cpu().numpy().view(np.uint64), g_d.cpu().numpy(), g_c.cpu().numpy().view(np.uint32)
+        for k, (o_ids, o_d, _, _) in enumerate(want):
+            c = len(o_ids)
+            assert int(g_c[k]) == c, (narrow, k, int(g_c[k]), c)
+            assert np.array_equal(g_ids[k, :c], o_ids) and np.array_equal(bits(g_d[k, :c]), bits(o_d)), (narrow, k)
+            assert not g_ids[k, c:].any() and not bits(g_d[k, c:]).any(), (narrow, k)  # exactly zero behind the count
+            assert start_id not in g_ids[k, :c], (narrow, k)
+        traces.append([x.cpu().numpy() for x in (tr.n_dist, tr.n_hop, tr.n_edges, tr.visit_ids)])
+    for k, (_, _, o_vis, o_tr) in enumerate(want):
+        assert int(traces[0][0][k]) == o_tr.n_dist and int(traces[0][1][k]) == o_tr.n_hop, k
+        assert np.array_equal(traces[0][3][k, :o_tr.n_hop].view(np.uint64), o_vis), k
+    for narrow, t in zip(narrows[1:], traces[1:]):
+        for a, b in zip(traces[0][:3], t[:3]):  # n_dist, n_hop, n_edges
+            assert np.array_equal(a, b), narrow
+        for k in range(nq):  # the visit log, as far as the walk went
+            assert np.array_equal(traces[0][3][k, :traces[0][1][k]], t[3][k, :t[1][k]]), (narrow, k)
     ix.close()
     gpq.close()
 

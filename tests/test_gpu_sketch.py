@@ -1,4 +1,4 @@
-"""The two-precision hop (SDB_TUNE_SKETCH, search_kernel.h FirstStage::keep): a float16 copy of the rows is read
+"""The two-precision hop (SDB_TUNE_SKETCH, walk_stage.h FirstStage::keep): a float16 copy of the rows is read
 first and a neighbour's float32 row only when its float16 distance does not PROVE that AddWithLimit discards it
 (distset.go:184).  Everything a search returns -- ids, distance bits, counts, visit order, n_dist / n_hop / n_edges --
 must be what the default walk and the oracle return; the audit mode evaluates every discarded neighbour exactly as

@@ -1,4 +1,4 @@
-"""The staged hop after its copy-row loads became global loads issued for EVERY hop (search_kernel.h FirstStage::begin).
+"""The staged hop after its copy-row loads became global loads issued for EVERY hop (walk_stage.h FirstStage::begin).
 
 What that change makes newly reachable, each against the float32 walk (knob 0) on the same index and against the oracle,
 bit for bit -- ids, distance bits, counts, n_dist / n_hop / n_edges, visit order:

@@ -1,7 +1,7 @@
 """The visited set's spill from LDS to the HBM bitset, forced in the middle of the walk in every walk kernel that has one.
 
 A query that has marked more than `hash_limit` ids clears its bitset, replays its LDS table into it and carries on there
-(search_kernel.h HashVisited::spill).  Test tables are too small to reach the default limit of 6000, so each batch here
+(visited_set.h HashVisited::spill).  Test tables are too small to reach the default limit of 6000, so each batch here
 runs at hash_limit = T for every T of a sweep (tests/visited_spill_model.py): 0 (the control: nothing spills), 1 (in the
 start node's row), 63 and 64 (either side of one full chunk), lo // 2 (mid-walk, the candidate array full, a first stage
 discarding), lo - 2 (every query within its last marks) and the batch's median (about half the waves of a launch spill),

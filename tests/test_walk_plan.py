@@ -104,6 +104,26 @@ def test_plan_beyond_what_a_tiny_table_reaches(program):
     assert re.search(r"grid: \d{5,} plans, [1-9]\d* staged above searchSize 96", out), out[-3000:]
 
 
+def test_dirty_buffer_settings_reach_every_result_copy(program, tmp_path):
+    """tests/test_gpu_pq.py test_result_rows_into_dirty_buffers says which caller of write_results each of its five
+    settings reaches; nothing a search call returns tells the callers apart, so the plan of each setting is held here:
+    60 rows, limit = searchSize = 64, 8 queries, K = 32; the fields as search_batch.hip fills them for a quantized table
+    (the table goes to LDS up to 64 KB)"""
+    want = {(128, 0): "sdb::k_greedy_search_pqw<15, 17, 4294967295u, 4, 15, true>",   # the split form: PQWideDist::serve<true>
+            (128, 3): "sdb::k_greedy_search_pqw<15, 17, 4294967295u, 4, 15, false>",  # the walker's own search_body
+            (128, 1): "sdb::k_greedy_search<sdb::PQDistT<true, true>, 2, false, 0u>",        # one wave, on the bitset
+            (8, 0): "sdb::k_greedy_search_pq2<4294967295u>",                           # pq2_merger
+            (8, 1): "sdb::k_greedy_search<sdb::PQDistT<true, true>, 2, false, 4294967295u>"}
+    keys = sorted(want)
+    lines = [_line({"nq": 8, "ng": 1, "tail": 0, "metric": 1, "search_size": 64, "words_per_query": 2, "filt": 0, "stage": 0,
+                    "prefer_bitset": 0, "wide_hash": 0, "wide_mode": 0, "pq_narrow": narrow, "pq": 1, "pq_M": M, "pq_K": 32,
+                    "pq_lut_in_lds": int(M * 32 * 4 <= 64 * 1024)}) for M, narrow in keys]
+    path = tmp_path / "dirty.txt"
+    path.write_text("".join(line + "\n" for line in lines))
+    plans = [dict(tok.split("=") for tok in ln.split()) for ln in _run([program, "plans", str(path)]).splitlines()]
+    assert [kernel_of(p) for p in plans] == [want[k] for k in keys]
+
+
 def test_golden_record_is_small():
     others = [os.path.getsize(os.path.join(os.path.dirname(GOLDEN), f)) for f in os.listdir(os.path.dirname(GOLDEN))
               if f.endswith(".npz")]
@@ -123,5 +143,8 @@ def test_callers_and_launcher_read_one_plan():
     assert src["walk_launch.hip"].count("hipLaunchKernelGGL") == 1
     assert 'fail(SDB_ERR_INVALID, "searchSize %u not supported on device (1..512)", a.search_size)' in src["walk_launch.hip"]
     assert [f for f, text in src.items() if '#include "search_kernel.h"' in text] == ["walk_launch.hip"]
+    for part in ("walk_stage.h", "walk_dist_rows.h", "cand_array.h", "visited_set.h", "walk_dist_codes.h"):  # search_kernel.h's parts
+        assert part in src and '#include "%s"' % part in src["search_kernel.h"], part
+        assert not [f for f, text in src.items() if f.endswith(".hip") and '#include "%s"' % part in text], part
     for f in ("walk_args.h", "walk_plan.h"):  # HIP-free outside a HIP build
         assert not re.search(r"__device__|__global__|hipStream_t", src[f]), f

@@ -1,6 +1,6 @@
 """The inputs of the forced visited-set spill tests, and the conditions that make them spill.
 
-Every hash-set walk keeps its visited set in an LDS table (search_kernel.h HashVisited) and, once a query has marked
+Every hash-set walk keeps its visited set in an LDS table (visited_set.h HashVisited) and, once a query has marked
 more than `hash_limit` ids (default 6000 = kHashLimit), replays the table into the query's HBM bitset and carries on
 there, in the middle of the walk.  A test table of a few thousand rows never marks 6000 ids, so the tests lower the
 limit: tests/test_gpu_visited_spill.py runs each batch below at hash_limit = T for every T of `Case.sweep()` and asks for

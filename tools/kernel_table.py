@@ -127,7 +127,7 @@ def disassembly(so=SO, match=r"^sdb::k_greedy_search"):
     return out
 
 
-# the staged one-wave kernels whose hop asks for the copy rows of all 64 edges ahead (search_kernel.h stage_ahead)
+# the staged one-wave kernels whose hop asks for the copy rows of all 64 edges ahead (walk_stage.h stage_ahead)
 AHEAD = re.compile(r"^sdb::k_greedy_search<sdb::(Int8Dist<(1|2|3)>|PlainDist<(1|2|3), (false|true), true, 4, \(sdb::Stage\)1>), ")
 
 
