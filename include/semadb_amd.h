@@ -425,6 +425,10 @@ int sdb_index_export(const sdb_index *ix, uint64_t *ids, float *vectors, uint64_
  * counts[s][q]) -- e.g. the buffer an RCCL all-gather produced -- sort by HybridScore
  * descending (= distance ascending for weight > 0) and truncate to `limit`.  The reference's
  * sort is unstable on arrival-ordered input; ties here break by (shard, id) ascending.
+ * The order is cmp.Compare's (actions.go:362-364), a total one: NaN distances are ONE tie class
+ * behind +Inf (broken by (shard, id) like any tie), -Inf comes first, -0.0 ties with 0.0; the
+ * distances come out with the bits they came in with.  A single shard (n_shards == 1) is not
+ * sorted at all (actions.go:357), NaN or not.
  * out_shards (optional) receives the originating shard.  Buffers follow `mem`. */
 int sdb_topk_merge(uint32_t n_shards, uint64_t nq, uint32_t per_shard, const uint64_t *ids,
                    const float *dists, const uint32_t *counts, uint32_t limit, uint64_t *out_ids,

@@ -1213,15 +1213,26 @@ typedef struct {
   float dist;
   int shard;
   uint64_t id;
+  int pos; /* place in the gathered list: the last tie-break, so that the order is total whatever qsort does */
 } merge_item;
+
+/* Go's cmp.Compare on floats: a total order -- NaN is less than every number and equal to NaN, -0.0 equals 0.0 */
+static int go_cmp_compare(float x, float y) {
+  const int x_nan = x != x, y_nan = y != y;
+  if (x_nan) return y_nan ? 0 : -1;
+  if (y_nan) return 1;
+  return x < y ? -1 : x > y ? 1 : 0;
+}
 
 static int merge_cmp(const void *a, const void *b) {
   const merge_item *x = a, *y = b;
-  if (x->score > y->score) return -1; /* cmp.Compare(b.HybridScore, a.HybridScore) :362-364 */
-  if (x->score < y->score) return 1;
+  /* cmp.Compare(b.HybridScore, a.HybridScore) :362-364: score descending, the NaN scores (NaN distances) last and
+   * tied with each other.  `>` / `<` alone are no order once a NaN is among the items. */
+  const int c = go_cmp_compare(y->score, x->score);
+  if (c) return c;
   if (x->shard != y->shard) return x->shard < y->shard ? -1 : 1;
   if (x->id != y->id) return x->id < y->id ? -1 : 1;
-  return 0;
+  return x->pos < y->pos ? -1 : x->pos > y->pos ? 1 : 0;
 }
 
 int orc_cluster_merge(int n_shards, const int *counts, const uint64_t *ids, const float *dists,
@@ -1237,6 +1248,7 @@ int orc_cluster_merge(int n_shards, const int *counts, const uint64_t *ids, cons
       it[n].score = -1 * it[n].dist * weight; /* vamana.go:303 */
       it[n].shard = s;
       it[n].id = ids[(size_t)s * per_shard_cap + i];
+      it[n].pos = n;
     }
   if (n_shards > 1) qsort(it, n, sizeof(merge_item), merge_cmp); /* actions.go:357 */
   if (n > limit) n = limit;                                       /* :372-374 */

@@ -163,7 +163,9 @@ int orc_shard_limit(int limit, int n_shards, int max_search_limit);
 /* Merge n_shards result lists (dists ascending per shard) for one query: sort by
  * HybridScore = -dist * weight descending (actions.go:357-364), truncate to limit (:372-374).
  * The reference sort is unstable on arrival-ordered input; the oracle uses the total order
- * (score desc, shard asc, id asc).  Returns count written. */
+ * (score desc, shard asc, id asc, place in the gathered list asc), scores compared like Go's
+ * cmp.Compare: NaN below every number and equal to NaN, so NaN distances are one tie class at
+ * the end; -0.0 equals 0.0.  A single shard is not sorted.  Returns count written. */
 int orc_cluster_merge(int n_shards, const int *counts, const uint64_t *ids, const float *dists,
                       int per_shard_cap, float weight, int limit, uint64_t *out_ids,
                       float *out_dists, int *out_shards);

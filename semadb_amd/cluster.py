@@ -42,7 +42,9 @@ def topk_merge(ids, dists, counts, limit, device=0):
     """ids/dists [n_shards, nq, per_shard], counts [n_shards, nq] -> merged (ids, dists, shards, counts).
 
     numpy in -> numpy out; torch CUDA in -> torch out on the current stream.  Ties break by
-    (shard, id) ascending (the reference's sort is unstable there, actions.go:357-364)."""
+    (shard, id) ascending (the reference's sort is unstable there, actions.go:357-364).  NaN distances
+    sort as cmp.Compare sorts them: one tie class behind +Inf, broken by (shard, id) too; -0.0 ties
+    with 0.0.  A single shard comes back as it arrived."""
     if _buf.is_torch_cuda(ids):
         import torch
         n_shards, nq, per = ids.shape

@@ -53,9 +53,22 @@ __device__ __forceinline__ bool tags_agree(uint32_t n_shards, const char *tags_b
   return ok;
 }
 
-// one 64-thread block per query; rank-by-counting under the total order (dist, shard, id, position) -- the
+// The reference sorts with cmp.Compare(b.HybridScore, a.HybridScore) (actions.go:362-364), HybridScore = -dist * weight:
+// a total order in which NaN is below every number and equal to NaN and -0.0 equals 0.0.  Read in distances (weight > 0):
+// -Inf first, +Inf last among the numbers, the NaN distances one tie class behind it.  `<` and `==` on floats are both
+// false against a NaN, so each distance is mapped ONCE, when it is staged, to an unsigned key with
+//   key(a) < key(b)  <=>  a before b,     key(a) == key(b)  <=>  a ties with b     (both zeros share a key, all NaNs the top one)
+// and the rank loop compares integers.  No float arithmetic: a denormal keeps a key of its own.
+__device__ __forceinline__ uint32_t merge_order_key(float d) {
+  if (d != d) return 0xFFFFFFFFu;  // no number maps here: 0xFFFFFFFF would be the image of a NaN's own bit pattern
+  const uint32_t b = __float_as_uint(d);
+  if (b == 0x80000000u) return 0x80000000u;  // -0.0 ties with 0.0
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// one 64-thread block per query; rank-by-counting under the total order (key of dist, shard, id, position) -- the
 // position only matters for a caller that hands in the same (dist, shard, id) twice: every item still gets a
-// rank of its own
+// rank of its own in [0, total)
 //
 // The three per-shard arrays are addressed as base + shard * stride (bytes): separate shard-major arrays
 // (stride = the array's own per-shard size) or the packed blocks an all-gather delivers back to back
@@ -68,7 +81,7 @@ __global__ __launch_bounds__(64) void k_topk_merge(uint32_t n_shards, uint64_t n
                                                    float *__restrict__ out_dists, uint32_t *__restrict__ out_shards,
                                                    uint32_t *__restrict__ out_counts, const char *__restrict__ tags_b,
                                                    size_t tag_stride, ExchangeVerdict *verdict) {
-  __shared__ float s_d[kMergeMaxItems];
+  __shared__ uint32_t s_key[kMergeMaxItems];  // merge_order_key of the distance; the distance itself is re-read for the output
   __shared__ uint64_t s_id[kMergeMaxItems];
   __shared__ uint16_t s_sh[kMergeMaxItems];
   __shared__ uint32_t s_off[65];
@@ -93,23 +106,25 @@ __global__ __launch_bounds__(64) void k_topk_merge(uint32_t n_shards, uint64_t n
     const uint32_t c = s_off[s + 1] - s_off[s];
     for (uint32_t i = t; i < c; i += 64) {
       const size_t src = (size_t)q * per_shard + i;
-      s_d[s_off[s] + i] = reinterpret_cast<const float *>(dists_b + (size_t)s * dists_stride)[src];
+      s_key[s_off[s] + i] = merge_order_key(reinterpret_cast<const float *>(dists_b + (size_t)s * dists_stride)[src]);
       s_id[s_off[s] + i] = reinterpret_cast<const uint64_t *>(ids_b + (size_t)s * ids_stride)[src];
       s_sh[s_off[s] + i] = (uint16_t)s;
     }
   }
   __syncthreads();
-  // HybridScore = -dist * weight descending (actions.go:362-364) == dist ascending for weight > 0
+  // HybridScore = -dist * weight descending (actions.go:362-364) == key ascending for weight > 0
   for (uint32_t i = t; i < total; i += 64) {
-    const float d = s_d[i];
+    const uint32_t k = s_key[i];
     const uint64_t id = s_id[i];
     const uint16_t sh = s_sh[i];
+    // the distance as it came in (the sign of a zero, a NaN's payload): item i is entry i - s_off[sh] of its shard's list
+    const float d = reinterpret_cast<const float *>(dists_b + (size_t)sh * dists_stride)[(size_t)q * per_shard + (i - s_off[sh])];
     uint32_t rank = 0;
     for (uint32_t j = 0; j < total; j++) {
-      const float dj = s_d[j];
+      const uint32_t kj = s_key[j];
       // a single shard is not re-sorted at all (actions.go:357: `if len(col.ShardIds) > 1`)
       const bool before = n_shards == 1 ? (j < i)
-                                        : (dj < d || (dj == d && (s_sh[j] < sh || (s_sh[j] == sh && (s_id[j] < id || (s_id[j] == id && j < i))))));
+                                        : (kj < k || (kj == k && (s_sh[j] < sh || (s_sh[j] == sh && (s_id[j] < id || (s_id[j] == id && j < i))))));
       rank += before ? 1u : 0u;
     }
     if (rank < limit) {  // truncate to the original limit (actions.go:372-374)

@@ -474,6 +474,7 @@ uint64_t hash_queries(const float *q, uint64_t n) {
 }
 
 // what exchange_shared + k_topk_merge do: compare the tags, merge by (distance, shard, id); group lock held
+// (plain `<` on the distance: the fake walk only produces finite ones, so k_topk_merge's NaN-last rule is not restated here)
 void mock_exchange(std::vector<MockArrival> &arr) {
   std::sort(arr.begin(), arr.end(), [](const MockArrival &a, const MockArrival &b) { return a.c->rank < b.c->rank; });
   const MockTag &t0 = arr[0].slot->tag;

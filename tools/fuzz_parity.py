@@ -751,7 +751,10 @@ def int8_trial(rng, device=True, spill_rng=None):
 
 
 def merge_trial(rng):
-    """the shard fan-out's merge (cluster/actions.go:357-376) on random ragged per-shard results with ties"""
+    """the shard fan-out's merge (cluster/actions.go:357-376) on random ragged per-shard results with ties, and once
+    more with NaN, +-Inf, +-0.0 and denormals drawn into the same lists (the oracle orders them like cmp.Compare).
+    The special values come from a generator of their own: `rng` is left where the finite trial alone leaves it, so
+    the trials that follow draw what they always drew."""
     from semadb_amd import cluster
     n_shards = int(rng.integers(1, 17))
     per = int(rng.integers(1, 76))
@@ -762,13 +765,25 @@ def merge_trial(rng):
         d = -d[:, :, ::-1].copy()  # dot-product distances are negative
     ids = rng.integers(2, 10 ** 6, size=(n_shards, nq, per)).astype(np.uint64)
     counts = rng.integers(0, per + 1, size=(n_shards, nq)).astype(np.uint32)
-    o_ids, o_d, o_s, o_c = cluster.topk_merge(ids, d, counts, limit)
-    for q in range(nq):
-        w_ids, w_d, w_s = orc.cluster_merge(ids[:, q, :], d[:, q, :], counts[:, q].astype(np.int32), limit)
-        n = len(w_ids)
-        assert int(o_c[q]) == n, ("merge count", n_shards, per, limit, q)
-        assert np.array_equal(o_ids[q, :n], w_ids) and np.array_equal(bits(o_d[q, :n]), bits(w_d)), ("merge", q)
-        assert np.array_equal(o_s[q, :n].astype(np.int32), w_s), ("merge shards", q)
+
+    def compare(d):
+        o_ids, o_d, o_s, o_c = cluster.topk_merge(ids, d, counts, limit)
+        for q in range(nq):
+            w_ids, w_d, w_s = orc.cluster_merge(ids[:, q, :], d[:, q, :], counts[:, q].astype(np.int32), limit)
+            n = len(w_ids)
+            assert int(o_c[q]) == n, ("merge count", n_shards, per, limit, q)
+            nan = np.isnan(w_d)  # the same bits, or NaN where the oracle has NaN (finite lists: bit for bit)
+            assert np.array_equal(o_ids[q, :n], w_ids) and np.array_equal(np.isnan(o_d[q, :n]), nan), ("merge", q)
+            assert np.array_equal(bits(o_d[q, :n])[~nan], bits(w_d)[~nan]), ("merge distances", q)
+            assert np.array_equal(o_s[q, :n].astype(np.int32), w_s), ("merge shards", q)
+
+    compare(d)
+    own = np.random.default_rng([n_shards, per, limit, nq, int(ids[0, 0, 0])])
+    special = np.array([0x7FC00000, 0xFFC12345, 0x7F800000, 0xFF800000, 0, 0x80000000, 1, 0x80000001], dtype=np.uint32)
+    d = np.ascontiguousarray(d).copy()
+    hit = own.random(d.shape) < float(own.choice([0.02, 0.3, 1.0]))
+    d.view(np.uint32)[hit] = special[own.integers(0, len(special), int(hit.sum()))]
+    compare(d)
 
 
 def pq_trial(rng):
