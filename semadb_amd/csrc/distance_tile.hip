@@ -313,7 +313,7 @@ __global__ __launch_bounds__(kK1L2Waves * 64) void k_k1_tile_pk(const float *__r
                                                                 float *__restrict__ out, uint64_t nc, uint32_t nq,
                                                                 uint32_t dim, uint32_t nblk, uint32_t tail,
                                                                 uint32_t tile_rows, int metric) {
-  // [tile_rows][kstride]: as many rows as fit LDS, at most one per lane (64 up to d = 608, 52 at 768, 39 at 1024)
+  // [tile_rows][kstride]: as many rows as fit LDS, at most one per lane (64 up to d = 632, 53 at 768, 39 at 1024, 9 at 4096)
   extern __shared__ __attribute__((aligned(16))) float tile[];
   const uint32_t kstride = dim + 4;  // +16 B per row: lane r starts at bank 4r, the lanes' ds_read_b128 never collide
   const int tid = threadIdx.x, lane = tid & 63;

@@ -84,7 +84,7 @@ TILE_DIMS = [32, 36, 64, 96, 100, 128, 160, 300, 384, 416, 608, 640, 768, 1024, 
 def test_tiled_distance_bit_exact(oracle, metric, d):
     """more queries than one operand group, candidate counts that leave ragged tiles, rows with and without a tail
     chain (d % 32 = 4, 12), every register-block count of the matrix-core kernel, euclidean tiles of fewer than 64
-    rows (d > 608), and the shapes past the tile kernels' reach, which fall back to the first kernel -- all
+    rows (d > 632), and the shapes past the tile kernels' reach, which fall back to the first kernel -- all
     bit-identical to the oracle"""
     from semadb_amd import distance
     rng = np.random.default_rng(d * 11 + len(metric))
@@ -97,12 +97,13 @@ def test_tiled_distance_bit_exact(oracle, metric, d):
 
 
 @pytest.mark.parametrize("metric", ["cosine", "dot"])
-@pytest.mark.parametrize("d", [64, 384, 416, 1024])
+@pytest.mark.parametrize("d", [64, 384, 416, 420, 1024])
 def test_tiled_distance_query_blocks(oracle, metric, d):
     """the two matrix-core kernels meet at 256 queries: up to there the queries stay in registers, 64 per workgroup
     (one, two, four query blocks, a ragged last one) and the candidates stream in spans of 512 (one span, a ragged
-    second and third); above, the candidate rows stay in registers and the query groups stream.  d = 416 has a tail
-    (always the second kernel), d = 1 024 is the longest row of the first"""
+    second and third); above, the candidate rows stay in registers and the query groups stream.  d = 416 is thirteen
+    whole blocks without a tail (the first block count past the change of __launch_bounds__), d = 420 is thirteen blocks and a tail of
+    4 (always the second kernel, at every query count), d = 1 024 is the longest row of the first"""
     from semadb_amd import distance
     rng = np.random.default_rng(d * 13 + len(metric))
     for nq, nc in [(64, 512), (65, 600), (130, 1100), (256, 513), (257, 520), (300, 1030)]:
