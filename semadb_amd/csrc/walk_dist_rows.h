@@ -23,6 +23,14 @@ struct PlainDist {
   // for it before AddWithLimit runs (search_body's kSpeculate path without the small-call kernel's marker wave) was
   // measured there too: 0.716 against 0.722 ms (min of 10), within the noise -- the naming costs about what the hidden
   // round trip saves.  Off.
+  // ... and on the int8 walk WITHOUT naming anything: both rows the next hop can go to -- the array's first unvisited
+  // entry as it stands, and the nearest new point (a wave minimum by DPP, one ballot) -- asked for before AddWithLimit
+  // and taken from the register when the walk goes there, which it does in 0.987 of the hops.  Per hop the adjacency
+  // row fell from 1 468 to 481 cycles and AddWithLimit ROSE from 3 038 to 4 283 (the hop 13 117 -> 13 351): this
+  // compiler waits for the two loads (s_waitcnt vmcnt(0)) at the first instruction of AddWithLimit that overwrites the
+  // temporary their address was computed in, with a scalar base and a long-lived offset register too, so the round
+  // trip moved and did not vanish, and the ~75 instructions of asking were added.  bench.py 2.059 - 2.079 M queries/s
+  // against 2.121 - 2.141 M, five alternating runs: a loss.  Left out (HISTORY.md).
   static constexpr bool kSpeculate = false;
   static constexpr bool marked = false;  // (no marker wave: nothing is tested ahead)
   __device__ __forceinline__ void take_marks(int, uint64_t &, uint32_t &) {}

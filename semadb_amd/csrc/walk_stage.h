@@ -206,13 +206,30 @@ struct Int8Rows {
 
 // One stage of the transposing butterfly: at stride S a lane keeps the rows whose bit S equals its own and hands the
 // others to lane ^ S.
+// No exchange goes through the LDS pipe (each was a ds_swizzle behind two selects):
+//   * stride 16: v_permlane16_swap(w[i], w[i + 16]) leaves, in every lane, what it keeps in one register and what it
+//     receives in the other -- the result is their sum;
+//   * strides 8 .. 1: a lane keeps w[i] and receives its partner's w[i], or the same of w[i + S]: both sums as DPP adds
+//     (row_ror:8; row_shl:4 for the lanes that keep w[i], row_shr:4 for the others; quad_perm), one select between
+//     them -- a lane a shift reads from outside its row adds 0 to the sum the select does not take.
+// (keep + received or received + keep: float adds commute, the float16 stage's bits are what they were.)
+template <int CTRL, class T>
+__device__ __forceinline__ T dpp_from(T v) {  // v of the lane CTRL names (0 from outside the row)
+  return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
 template <int S, class T>
 __device__ __forceinline__ void butterfly_stage(T (&w)[32], int lane) {
-  const bool up = (lane & S) != 0;
 #pragma unroll
   for (int i = 0; i < S; i++) {
-    const T keep = up ? w[i + S] : w[i], send = up ? w[i] : w[i + S];
-    w[i] = keep + __builtin_bit_cast(T, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, send), (S << 10) | 0x1F));
+    if constexpr (S == 16) {
+      const auto sw = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, w[i]), __builtin_bit_cast(uint32_t, w[i + S]), false, false);
+      w[i] = __builtin_bit_cast(T, (uint32_t)sw[0]) + __builtin_bit_cast(T, (uint32_t)sw[1]);
+    } else {
+      // lane ^ S, for the lanes without / with bit S
+      constexpr int kLo = S == 8 ? 0x128 : S == 4 ? 0x104 : S == 2 ? 0x4E : 0xB1, kHi = S == 4 ? 0x114 : kLo;
+      const T lo = w[i] + dpp_from<kLo>(w[i]), hi = w[i + S] + dpp_from<kHi>(w[i + S]);
+      w[i] = (lane & S) ? hi : lo;
+    }
   }
 }
 // 32 sums per half-wave (pair u: edge 2u in lanes 0..31, edge 2u + 1 in lanes 32..63), each spread over the 32 lanes.
@@ -288,10 +305,17 @@ struct FirstStage {
       const gbytes baseL = as_global(static_cast<const char *>(cold_args(a).sketch)) + L * Fmt::kLaneBytes;
       const uint32_t row_bytes = a.ld * Fmt::kElemBytes;
       const uint32_t safe = valid ? nb : a.start_slot;  // an edge that is not there: any row (its result is not looked at)
+      // pair u's slot: edge 2u for lanes 0..31, edge 2u + 1 for lanes 32..63 -- ONE ds_bpermute of `safe` from lane
+      // 2u + hi, the constant 8u in the instruction's offset field (two readlanes, two moves and a select before);
+      // with the 64-bit mad that is two vector instructions in front of a row's load
+      // (`pick` is made opaque per hop: as a value the compiler knows across hops, the 32 sums pick + 8u were hoisted
+      // out of the walk into 32 registers; inside the hop they fold into the offset field)
+      int pick = hi ? 4 : 0;
+      asm volatile("" : "+v"(pick));
 #pragma unroll
       for (int u = 0; u < 32; u++) {
-        const uint32_t s0 = rl(safe, 2 * u), s1 = rl(safe, 2 * u + 1);
-        Fmt::load(y[u], baseL + (uint64_t)(hi ? s1 : s0) * row_bytes);
+        const uint32_t s = (uint32_t)__builtin_amdgcn_ds_bpermute(pick + 8 * u, (int)safe);
+        Fmt::load(y[u], baseL + (uint64_t)s * row_bytes);
       }
       if constexpr (L2) fmt.yy = as_global(cold_args(a).sketch_norm)[safe];
       loaded = full;
