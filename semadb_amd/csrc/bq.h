@@ -58,6 +58,4 @@ int bq_encode_device(const float *d_thr, uint32_t dim, const float *d_vecs, uint
 int bq_fit_slab(const RowLayout &l, const float *d_slab, const uint64_t *d_ids, uint32_t n, float *d_thr, hipStream_t stream);
 int bq_encode_slab(const float *d_thr, const RowLayout &l, const float *d_slab, uint32_t first, uint32_t n, uint64_t *d_codes,
                    hipStream_t stream);
-// binaryQuantizer.Set (binary.go:131-139) for slab rows [first, first + n) of an index with a binary quantizer attached (index.hip)
-int encode_bit_rows_public(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream);
 }  // namespace sdb

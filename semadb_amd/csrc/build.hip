@@ -1248,10 +1248,6 @@ using namespace sdb;
 // defined in index.hip
 extern "C" int sdb_index_stats(const sdb_index *ix, uint64_t *n_nodes, uint64_t *n_edges, uint64_t *max_node_id);
 
-namespace sdb {
-int store_rows_public(sdb_index *ix, uint32_t first, uint32_t n, const float *dev_vectors, hipStream_t stream);
-}
-
 extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t *ids, const float *vectors, int mem,
                                       uint32_t round_size, void *stream_) try {
   if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
@@ -1483,13 +1479,13 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     dvec = staging;
   }
   // vecStore.Set for the whole batch (insert.go:17): rows are unreachable until they get in-edges
-  SDB_W_TRY(store_rows_public(ix, n0, (uint32_t)n, dvec, stream));
+  SDB_W_TRY(store_rows(ix, n0, (uint32_t)n, dvec, SDB_MEM_DEVICE, stream));
   // a fitted quantizer encodes on Set (product.go:161-169); from here on every distance of the insert is a
   // table distance: LUT for the search (DistanceFromFloat), centroid pairs for the prunes (DistanceFromPoint)
   if (pq) SDB_W_TRY(pq_encode_device(pq, dvec, n, ix->d_codes + (size_t)n0 * pq->M, stream));
   // ... and so does the binary quantizer (binary.go:131-139): the insert's search and prunes read these code rows
   if (bq) SDB_W_TRY(bq_encode_device(bq->d_thr, l.dim, dvec, n, reinterpret_cast<uint64_t *>(ix->d_codes) + (size_t)n0 * bq->W, stream));
-  SDB_W_HIP(hipMemcpyAsync(ix->d_ids + n0, new_ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  SDB_W_HIP(hipMemcpyAsync(ix->wr.ids + n0, new_ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
   // host-side id bookkeeping of the points of one completed round: h_ids / id2slot / max_node_id move together
   // with ix->n, so that an error return never leaves ids that resolve to slots past the rows in use
   auto commit = [&](uint64_t from, uint64_t to) {
@@ -1526,12 +1522,12 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     if (rs > n - done) rs = (uint32_t)(n - done);
     // ---- greedySearch(vec, 1, SearchSize, nil) for every point of the round (insert.go:22)
     SearchArgs sa{};
-    sa.slab = ix->d_slab, sa.adj = ix->d_adj, sa.ids = ix->d_ids;
+    sa.slab = ix->d_slab, sa.adj = ix->wr.adj, sa.ids = ix->wr.ids;
     sa.bitsets = bitsets, sa.words_per_query = words;
     sa.queries = dvec + done * l.dim;
     sa.dim = l.dim, sa.nblk = l.nblk, sa.ng = l.ng, sa.tail = l.tail, sa.ld = l.ld;
     sa.start_slot = (uint32_t)ix->start_slot;
-    sa.start_ext = ix->d_start_ext, sa.start_ext_n = (uint32_t)ix->h_start_ext.size();
+    sa.start_ext = ix->wr.start_ext, sa.start_ext_n = (uint32_t)ix->h_start_ext.size();
     sa.search_size = L, sa.limit = 1, sa.metric = (int)ix->P.metric;
     sa.vis_slots = vis_slots, sa.vis_dists = vis_dists, sa.vis_count = vis_count, sa.vis_cap = vis_cap;
     sa.hash_limit = ix->tune_hash_limit, sa.prefer_bitset = ix->tune_no_hash ? 1u : 0u;
@@ -1559,7 +1555,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     SDB_W_TRY(launch_walk_plan(plan, sa, rs, stream));  // read-only on the graph: a failure here adds nothing to what the rounds before it did
     // ---- robustPrune + back-edges
     BuildArgs ba{};
-    ba.slab = ix->d_slab, ba.adj = ix->d_adj, ba.deg = ix->d_deg, ba.clean = ix->d_clean;
+    ba.slab = ix->d_slab, ba.adj = ix->wr.adj, ba.deg = ix->d_deg, ba.clean = ix->d_clean;
     ba.adjdist = ix->d_adjdist, ba.dcount = ix->d_dcount;
     ba.dim = l.dim, ba.nblk = l.nblk, ba.ng = l.ng, ba.tail = l.tail, ba.ld = l.ld;
     ba.metric = (int)ix->P.metric, ba.alpha = ix->P.alpha, ba.R = ix->P.degree_bound;
@@ -1571,7 +1567,7 @@ extern "C" int sdb_index_insert_batch(sdb_index *ix, uint64_t n, const uint64_t 
     ba.dcache = dcache, ba.dcache_shift = 32 - kDcacheBits;
     ba.big_count = big_count, ba.big_list = big_list, ba.big_min = big_min, ba.big_cap = big_cap;
     ba.start_slot = (uint32_t)ix->start_slot;
-    ba.start_ext = ix->d_start_ext, ba.start_ext_n = (uint32_t)ix->h_start_ext.size();
+    ba.start_ext = ix->wr.start_ext, ba.start_ext_n = (uint32_t)ix->h_start_ext.size();
     ba.stats = reinterpret_cast<unsigned long long *>(ix->d_bstats), ba.flags = big_count + 1;
     ba.no_tile = ix->tune_no_tile, ba.prune_done = prune_done, ba.dirty = ix->d_dirty;
     ba.pair_tab = pair_tab, ba.pair_slots = pair_slots, ba.pair_dists = pair_dists;

@@ -309,7 +309,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
   SDB_HIP(hipMemcpyAsync(d_flags, h_del.data(), N, hipMemcpyHostToDevice, stream));
   SDB_HIP(hipMemsetAsync(d_flags + N, 0, (size_t)N * 2, stream));
   DeleteArgs a{};
-  a.b.slab = ix->d_slab, a.b.adj = ix->d_adj, a.b.deg = ix->d_deg, a.b.clean = ix->d_clean;
+  a.b.slab = ix->d_slab, a.b.adj = ix->wr.adj, a.b.deg = ix->d_deg, a.b.clean = ix->d_clean;
   a.b.adjdist = ix->d_adjdist, a.b.dcount = ix->d_dcount;
   a.b.dim = l.dim, a.b.nblk = l.nblk, a.b.ng = l.ng, a.b.tail = l.tail, a.b.ld = l.ld;
   a.b.metric = (int)ix->P.metric, a.b.alpha = ix->P.alpha, a.b.R = ix->P.degree_bound;
@@ -318,7 +318,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
   if (pq) a.b.pq_codes = ix->d_codes, a.b.pq_cdists = pq->d_cdists, a.b.pq_M = pq->M, a.b.pq_K = pq->K;
   const sdb_bq *bq = ix->bq;  // binary quantizer: the bit distance of two code rows (binary.go:213-223)
   if (bq) a.b.pq_codes = ix->d_codes, a.b.pq_M = ix->code_bytes;
-  a.ids = ix->d_ids, a.del = d_flags, a.has_inbound = d_flags + N, a.to_prune = d_flags + 2 * (size_t)N, a.n = N;
+  a.ids = ix->wr.ids, a.del = d_flags, a.has_inbound = d_flags + N, a.to_prune = d_flags + 2 * (size_t)N, a.n = N;
   uint32_t *d_bound = nullptr;
   SDB_HIP(hipMalloc(&d_bound, (size_t)N * 4));
   fr.p.push_back(d_bound);
@@ -420,7 +420,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
     SDB_HIP(hipStreamSynchronize(stream));
     auto fetch_row = [&](uint32_t node, std::vector<uint32_t> &out) -> int {
       uint32_t row[kAdjStride], deg = 0;
-      SDB_HIP(hipMemcpy(row, ix->d_adj + (size_t)node * kAdjStride, sizeof(row), hipMemcpyDeviceToHost));
+      SDB_HIP(hipMemcpy(row, ix->wr.adj + (size_t)node * kAdjStride, sizeof(row), hipMemcpyDeviceToHost));
       SDB_HIP(hipMemcpy(&deg, ix->d_deg + node, 4, hipMemcpyDeviceToHost));
       out.assign(row, row + (deg < kAdjStride ? deg : kAdjStride));
       return SDB_OK;
@@ -441,7 +441,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
     if (nc == 0) {
       std::vector<uint32_t> empty_row(kAdjStride, kNoSlot);
       const uint32_t zero = 0;
-      SDB_HIP(hipMemcpy(ix->d_adj + (size_t)st * kAdjStride, empty_row.data(), kAdjStride * 4, hipMemcpyHostToDevice));
+      SDB_HIP(hipMemcpy(ix->wr.adj + (size_t)st * kAdjStride, empty_row.data(), kAdjStride * 4, hipMemcpyHostToDevice));
       SDB_HIP(hipMemcpy(ix->d_dirty + st, &one, 1, hipMemcpyHostToDevice));
       SDB_HIP(hipMemcpy(ix->d_deg + st, &zero, 4, hipMemcpyHostToDevice));
       SDB_HIP(hipMemcpy(ix->d_clean + st, &zero, 4, hipMemcpyHostToDevice));
@@ -462,7 +462,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
   if (!to_save.empty()) {
     SDB_HIP(hipStreamSynchronize(stream));
     uint32_t row[kAdjStride];
-    SDB_HIP(hipMemcpy(row, ix->d_adj + (size_t)st * kAdjStride, sizeof(row), hipMemcpyDeviceToHost));
+    SDB_HIP(hipMemcpy(row, ix->wr.adj + (size_t)st * kAdjStride, sizeof(row), hipMemcpyDeviceToHost));
     uint32_t deg = 0;
     while (deg < kAdjStride && row[deg] != kNoSlot) deg++;
     // AddNeighbourIfNotExists (node.go:73-80) has no bound: past the 64 entries of the row the edges go on the
@@ -476,7 +476,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
       if (deg < kAdjStride && ext.empty()) row[deg++] = v;
       else ext.push_back(v);
     }
-    SDB_HIP(hipMemcpy(ix->d_adj + (size_t)st * kAdjStride, row, sizeof(row), hipMemcpyHostToDevice));
+    SDB_HIP(hipMemcpy(ix->wr.adj + (size_t)st * kAdjStride, row, sizeof(row), hipMemcpyHostToDevice));
     SDB_HIP(hipMemcpy(ix->d_dirty + st, &one, 1, hipMemcpyHostToDevice));
     SDB_HIP(hipMemcpy(ix->d_deg + st, &deg, 4, hipMemcpyHostToDevice));
     SDB_TRY(ix->sync_start_ext());
@@ -494,7 +494,7 @@ static int delete_batch_impl(sdb_index *ix, uint64_t n, const uint64_t *ids, voi
   }
   {
     SDB_HIP(hipMemcpyAsync(d_dead, dslots.data(), dslots.size() * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_tombstone, dim3((unsigned)dslots.size()), dim3(64), 0, stream, ix->d_adj, ix->d_deg, ix->d_ids,
+    hipLaunchKernelGGL(k_tombstone, dim3((unsigned)dslots.size()), dim3(64), 0, stream, ix->wr.adj, ix->d_deg, ix->wr.ids,
                        ix->d_dirty, d_dead);
     SDB_HIP(hipGetLastError());
   }
@@ -543,8 +543,8 @@ extern "C" int sdb_index_edge_scan(const sdb_index *ix, uint64_t n, const uint64
   SDB_HIP(hipMemcpyAsync(d_flags, h_del.data(), N, hipMemcpyHostToDevice, stream));
   SDB_HIP(hipMemsetAsync(d_flags + N, 0, (size_t)N * 2, stream));
   DeleteArgs a{};
-  a.b.adj = ix->d_adj, a.b.deg = ix->d_deg;
-  a.ids = ix->d_ids, a.del = d_flags, a.has_inbound = d_flags + N, a.to_prune = d_flags + 2 * (size_t)N, a.n = N;
+  a.b.adj = ix->wr.adj, a.b.deg = ix->d_deg;
+  a.ids = ix->wr.ids, a.del = d_flags, a.has_inbound = d_flags + N, a.to_prune = d_flags + 2 * (size_t)N, a.n = N;
   a.bound = d_bound;
   hipLaunchKernelGGL(k_edge_scan, dim3(N), dim3(64), 0, stream, a);
   SDB_HIP(hipGetLastError());
@@ -604,7 +604,7 @@ extern "C" int sdb_index_union_prune(sdb_index *ix, uint64_t id, uint64_t m, con
   hipStream_t stream = as_stream(stream_);
   const RowLayout &l = ix->lay;
   BuildArgs a{};
-  a.slab = ix->d_slab, a.adj = ix->d_adj, a.deg = ix->d_deg, a.clean = ix->d_clean;
+  a.slab = ix->d_slab, a.adj = ix->wr.adj, a.deg = ix->d_deg, a.clean = ix->d_clean;
   a.adjdist = ix->d_adjdist, a.dcount = ix->d_dcount;
   a.dim = l.dim, a.nblk = l.nblk, a.ng = l.ng, a.tail = l.tail, a.ld = l.ld;
   a.metric = (int)ix->P.metric, a.alpha = ix->P.alpha, a.R = ix->P.degree_bound;

@@ -898,9 +898,6 @@ SDB_API_CATCH("sdb_index_flat_search")
 
 // vecStore.Set for a flat index (flat.go:46-49): store vectors without touching the graph.
 namespace sdb {
-int store_rows_public(sdb_index *ix, uint32_t first, uint32_t n, const float *dev_vectors, hipStream_t stream);
-}
-namespace sdb {
 // vecStore.Delete on an index without a graph: the row becomes a tombstone (id 0), like a deleted graph node's
 __global__ void k_flat_tombstone(uint64_t *ids, uint8_t *dirty, const uint32_t *dead, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -947,7 +944,7 @@ static int flat_tombstone(sdb_index *ix, std::vector<uint32_t> &slots, bool *cha
   hipError_t e = hipMemcpy(d_dead, slots.data(), slots.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     *changed = true;
-    hipLaunchKernelGGL(sdb::k_flat_tombstone, dim3((unsigned)((slots.size() + 255) / 256)), dim3(256), 0, nullptr, ix->d_ids,
+    hipLaunchKernelGGL(sdb::k_flat_tombstone, dim3((unsigned)((slots.size() + 255) / 256)), dim3(256), 0, nullptr, ix->wr.ids,
                        ix->d_dirty, d_dead, (uint32_t)slots.size());
     e = hipGetLastError();
   }
@@ -1047,9 +1044,9 @@ extern "C" int sdb_index_set_vectors(sdb_index *ix, uint64_t n, const uint64_t *
     }
     dvec = staging;
   }
-  int rc = store_rows_public(ix, n0, (uint32_t)n, dvec, nullptr);
-  if (rc == SDB_OK && ix->bq) rc = encode_bit_rows_public(ix, n0, (uint32_t)n, nullptr);  // Set encodes (binary.go:131-139)
-  hipError_t e = hipMemcpy(ix->d_ids + n0, new_ids.data(), n * 8, hipMemcpyHostToDevice);
+  int rc = store_rows(ix, n0, (uint32_t)n, dvec, SDB_MEM_DEVICE, nullptr);
+  if (rc == SDB_OK && ix->bq) rc = encode_bit_rows(ix, n0, (uint32_t)n, nullptr);  // Set encodes (binary.go:131-139)
+  hipError_t e = hipMemcpy(ix->wr.ids + n0, new_ids.data(), n * 8, hipMemcpyHostToDevice);
   (void)hipDeviceSynchronize();
   if (staging) (void)hipFree(staging);
   if (rc != SDB_OK) return rc;

@@ -1,6 +1,7 @@
 // index.h -- host-side state of one HBM-resident Vamana index (internal; the public surface is
 // include/semadb_amd.h).
 #pragma once
+#include <array>
 #include <map>
 #include <shared_mutex>
 #include <thread>
@@ -69,6 +70,72 @@ struct Workspace {
 
 struct PQState;  // pq.hip
 
+// Freshly allocated device buffers, owned until they change hands: released by the destructor (or drop()) unless
+// keep() has been called.  Every buffer of a step is taken BEFORE anything of the index is replaced, so that a failed
+// allocation returns the ones before it and leaves the index as it was (reserve, sdb_index_compact).
+struct FreshBufs {
+  std::vector<void *> p;
+  FreshBufs() = default;
+  FreshBufs(const FreshBufs &) = delete;
+  FreshBufs &operator=(const FreshBufs &) = delete;
+  ~FreshBufs() { drop(); }
+  // (room for the pointer first: nothing here fails between an allocation and its being owned)
+  int get_bytes(void **out, size_t bytes) {
+    p.reserve(p.size() + 1);
+    SDB_HIP(hipMalloc(out, bytes));
+    p.push_back(*out);
+    return SDB_OK;
+  }
+  template <class T>
+  int get_n(T **out, size_t count) { return get_bytes(reinterpret_cast<void **>(out), count * sizeof(T)); }
+  // two buffers of a CACHE: both or neither, and no room for them is no error.  pair_if_room: the same without an
+  // owner, for buffers that go straight into the index (alloc_adjcodes); it does not throw.
+  static bool pair_if_room(void **a, void **b, size_t bytes) noexcept {
+    *a = *b = nullptr;
+    if (hipMalloc(a, bytes) == hipSuccess && hipMalloc(b, bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    if (*a) (void)hipFree(*a);
+    *a = *b = nullptr;
+    return false;
+  }
+  bool get_pair_if_room(void **a, void **b, size_t bytes) {
+    p.reserve(p.size() + 2);
+    if (!pair_if_room(a, b, bytes)) return false;
+    p.push_back(*a), p.push_back(*b);
+    return true;
+  }
+  void drop() {
+    for (void *x : p)
+      if (x) (void)hipFree(x);
+    p.clear();
+  }
+  void keep() { p.clear(); }
+};
+
+// One of the two copies of everything a walk reads and a write changes in place (sdb_index graph versions).
+struct GraphCopy {
+  uint32_t *adj = nullptr;        // [cap][kAdjStride] neighbour slots, kNoSlot padded, edge order kept
+  uint64_t *ids = nullptr;        // [cap] slot -> node id
+  uint32_t *start_ext = nullptr;  // the start node's overflow list, kNoSlot-padded to a multiple of 64 (sdb_index::h_start_ext)
+  uint32_t start_ext_cap = 0;
+  uint8_t *adjcodes = nullptr;    // [cap][kAdjStride][M] the neighbours' code rows, or NULL (sdb_index::has_adjcodes)
+  // room for `need` overflow entries: a buffer too small gives way to one of 2 * need, whose contents are for the
+  // caller to write (a failed allocation leaves the copy as it was).  Nothing may still read the old buffer.
+  int grow_start_ext(uint32_t need);
+};
+
+// One per-row device array of the index: where its pointer is kept, what a row of it takes, what byte a fresh one is
+// filled with, and whether the index can do without it (sdb_index::row_tables).
+struct RowTable {
+  enum Kind { kRequired, kQuantizer /* present with a quantizer only */, kCache /* may be dropped */ };
+  enum Id { kSlab, kWrAdj, kCmAdj, kDeg, kClean, kWrIds, kCmIds, kDirty, kAdjDist, kDCount, kCodes, kWrAdjCodes, kCmAdjCodes, kCount };
+  static constexpr int kNoFill = -1;
+  void **slot;
+  size_t row_bytes;  // 0: the index has none
+  int fill;          // 0xFF, 0 or kNoFill
+  Kind kind;
+};
+
 // Re-ranking of a walk's candidates by their stored float32 rows (rerank.hip k_rerank; semadb_amd.h
 // sdb_index_search_batch_rerank).  cand_*: what the walk wrote with limit = rerank; out_*: where the call's answer goes.
 struct RerankArgs {
@@ -95,6 +162,14 @@ int launch_rerank(const RerankArgs &a, uint32_t nq, hipStream_t stream);
 struct SearchArgs;
 struct WalkPlan;
 int launch_walk_plan(const WalkPlan &plan, const SearchArgs &a, uint32_t nq, hipStream_t stream);
+// index.hip: n original-layout rows (host or device memory, `mem`) into slab rows [first, first + n); slab rows back into
+// original layout at dst (device); binaryQuantizer.Set (binary.go:131-139) for slab rows of an index with a binary quantizer
+int store_rows(sdb_index *ix, uint32_t first, uint32_t n, const float *vectors, int mem, hipStream_t stream);
+int unpermute_rows(const sdb_index *ix, uint32_t first, uint32_t n, float *dst, hipStream_t stream);
+int encode_bit_rows(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream);
+// Are ids[0, n) dense (ids[i] == ids[0] + i, ids[0] != 0; or n == 0)?  `map` is cleared; if they are not, it gets
+// id -> slot of every id != 0, and *first_dup the first slot whose id was there already (n: none).
+bool index_ids(const uint64_t *ids, size_t n, std::unordered_map<uint64_t, uint32_t> &map, size_t *first_dup = nullptr);
 int launch_greedy_search(const SearchArgs &a, uint32_t nq, hipStream_t stream);  // plan, then launch, for a call whose bitsets are zero already: nothing here clears them
 // the device's address of page-locked host memory the kernels can read and write in place; false: pageable, or not mapped
 bool device_view_of_host(const void *p, size_t bytes, void **dev);
@@ -117,7 +192,6 @@ struct sdb_index {
   int64_t start_slot = -1;
   uint64_t max_node_id = 0;  // vamana.go:47
   float *d_slab = nullptr;   // [cap][lay.ld] float32, permuted rows (common.h RowLayout)
-  uint32_t *d_adj = nullptr; // [cap][kAdjStride] neighbour slots, kNoSlot padded, edge order kept
   uint32_t *d_deg = nullptr; // [cap]
   uint32_t *d_clean = nullptr; // [cap] leading edges of a row produced by its last robustPrune (build.hip)
   // write-path cache: d_adjdist[r][e] = distFn(r, adj[r][e]) for e < d_dcount[r] (a prefix of the row).  A full
@@ -126,15 +200,13 @@ struct sdb_index {
   // arithmetic -- so they are read back (256 B) instead of recomputed from 64 rows.  Full-precision store only.
   float *d_adjdist = nullptr;    // [cap][kAdjStride]
   uint32_t *d_dcount = nullptr;  // [cap]
-  uint64_t *d_ids = nullptr; // [cap] slot -> node id
   // The start node's edges beyond the 64 of its adjacency row.  Stragglers of a delete are appended to the start
   // node with no bound (AddNeighbourIfNotExists, node.go:73-80 / prune.go:131-151); the list stays that long until
   // the start node is next pruned (a back-edge from an insert, insert.go:47-58, or a delete among its edges).
   // Host copy in edge order; the device copy is padded with kNoSlot to a multiple of 64 so the search reads it in
   // row-sized chunks.  Every other node is bounded by DegreeBound <= 64.
   std::vector<uint32_t> h_start_ext;
-  uint32_t *d_start_ext = nullptr;
-  uint32_t start_ext_cap = 0;
+  uint32_t start_ext_need() const { return (uint32_t)((h_start_ext.size() + 63) / 64 * 64); }  // entries of the padded device copy
   std::vector<uint64_t> h_ids;
   bool dense_ids = true;  // ids[i] == ids[0] + i  (then no hash map is needed)
   std::unordered_map<uint64_t, uint32_t> id2slot;
@@ -155,24 +227,25 @@ struct sdb_index {
   // bytes).  One block per adjacency copy (graph versions below): searches read the committed one; the writer's is
   // brought up to date from the dirty-row flags when a transaction commits (k_adjcodes_rows) -- no write kernel
   // maintains it, and the build's own searches gather by slot as before.
-  uint8_t *d_adjcodes = nullptr;  // the writer's copy (beside d_adj)
-  uint8_t *r_adjcodes = nullptr;  // the committed copy (beside r_adj)
+  // (GraphCopy::adjcodes; index_codes.hip)
   static constexpr uint32_t kAdjCodesMaxM = 32;
-  bool has_adjcodes() const { return d_adjcodes != nullptr; }
+  bool has_adjcodes() const { return wr.adjcodes != nullptr; }
   int alloc_adjcodes();                       // after a quantizer has been attached (cap rows)
   int rebuild_adjcodes(hipStream_t stream);   // every row of both copies from (adjacency, codes); maintenance calls
+  // rows [0, rows) of g.adjcodes from (g.adj, codes; NULL: d_codes) on `stream`, not waited for; dirty != NULL: only the
+  // rows a transaction wrote or appended (`from`: rows at its start).  The one launch of k_adjcodes_rows.
+  int fill_adjcodes(const sdb::GraphCopy &g, uint32_t rows, const uint8_t *dirty, uint32_t from, hipStream_t stream,
+                    const uint8_t *codes = nullptr);
+  int forget_prune_state();  // d_clean / d_dcount start over: the store's distance function has changed (index_codes.hip)
   // ---- graph versions (SURVEY 8b Threading; shard/cache/manager.go:159-181) --------------------------------
   // A search walks the last COMMITTED graph while a write transaction changes the graph: everything a walk reads
   // and a write changes in place exists twice -- adjacency rows, the slot -> id table, the start node's overflow
-  // list.  d_adj / d_ids / d_start_ext above are the writer's copies (all write paths use them unchanged);
-  // r_adj / r_ids / r_start_ext are what `view` hands to searches.  Commit swaps the two sets and then brings the
-  // writer's (now stale) set up to date from the dirty-row flags the write kernels left, once the searches that
-  // were launched on it have drained (stream-side waits on their events).  Outside a transaction both sets are
-  // identical.  The slab is append-only (rows past view.n are invisible), so it exists once.
-  uint32_t *r_adj = nullptr;
-  uint64_t *r_ids = nullptr;
-  uint32_t *r_start_ext = nullptr;
-  uint32_t r_start_ext_cap = 0;
+  // list, and the neighbours' code rows (one GraphCopy each).  `wr` is the writer's copy (all write paths use it);
+  // `cm` is the committed one, which `view` hands to searches.  Commit swaps the two and then brings the writer's
+  // (now stale) copy up to date from the dirty-row flags the write kernels left, once the searches that were
+  // launched on it have drained (stream-side waits on their events).  Outside a transaction both are identical.
+  // The slab is append-only (rows past view.n are invisible), so it exists once.  (index_versions.hip)
+  sdb::GraphCopy wr, cm;
   uint8_t *d_dirty = nullptr;  // [cap] != 0: the open transaction wrote this row's adjacency or id
   struct View {
     uint32_t n = 0;  // committed rows
@@ -180,8 +253,14 @@ struct sdb_index {
     const uint64_t *ids = nullptr;
     const uint32_t *start_ext = nullptr;
     uint32_t start_ext_n = 0;
-    const uint8_t *adj_codes = nullptr;  // r_adjcodes, or NULL
+    const uint8_t *adj_codes = nullptr;  // cm.adjcodes, or NULL
   } view;
+  // view_mu held exclusively.  publish_pointers: `view` reads the committed copy's buffers as they are now (growth
+  // inside an open transaction: view.n and the transaction stay).  publish: that, with the rows and the overflow list
+  // of the writer's state, and the open transaction ends.
+  void publish_pointers();
+  void publish();
+  void end_tx();  // the transaction's host-side marks go (tx_dirty included)
   // readers: shared from taking `view` until their kernels are enqueued and their event recorded; writers:
   // exclusive while they change the host-side id tables or publish a view
   mutable sdb::ViewMutex view_mu;
@@ -220,7 +299,7 @@ struct sdb_index {
   uint32_t tune_wide_walk = 0;  // the workgroup-per-query walk of small calls: 0 = up to 256 queries, 1 = never, 2 = always
   bool tune_no_zero_copy = false;  // A/B and parity tests: host-memory searches stage even page-locked buffers
   // Two-precision hop (SDB_TUNE_SKETCH; walk_args.h SearchArgs::sketch): a float16 copy of the slab's rows, an
-  // optional cache like d_adjcodes.  It describes the rows of the view published as number `sketch_gen`; a search
+  // optional cache like GraphCopy::adjcodes.  It describes the rows of the view published as number `sketch_gen`; a search
   // uses it only while that is the current view.  Every path that publishes rows (load, commit, publish_full,
   // rollback, compact) brings it up to date behind the searches of the old view, and reserve() carries it across
   // table growth.  Pointers, capacity, maxima and generation change under the exclusive view_mu only (searches read
@@ -286,6 +365,16 @@ struct sdb_index {
   mutable std::vector<sdb::Workspace *> pool;
 
   int64_t slot_of(uint64_t id) const;
+  // Every per-row device array of the index (the two sketch buffers apart: they have a capacity and rules of their
+  // own, sketch_cap / sketch_room).  reserve, sdb_index_compact, sdb_index_destroy and sdb_index_load's undo go by it.
+  std::array<sdb::RowTable, sdb::RowTable::kCount> row_tables();
+  // A fresh set of row tables for `rows` rows, filled with their fill bytes; t[i] stays NULL where the index has no such
+  // table, and a kCache table there was no room for is NULL as well (the neighbour-code pair: both or neither).
+  // may_drop_sketch (the caller holds sketch_mu and not view_mu): a required allocation that fails while a sketch exists
+  // drops the sketch and is tried once more.
+  int alloc_row_tables(uint32_t rows, sdb::FreshBufs &fresh, std::array<void *, sdb::RowTable::kCount> &t, bool may_drop_sketch);
+  // view_mu held exclusively, device idle: the old tables are freed and `t` takes their place (fresh.keep()).
+  void adopt_row_tables(sdb::FreshBufs &fresh, const std::array<void *, sdb::RowTable::kCount> &t);
   int reserve(uint32_t rows);
   int sync_start_ext();  // h_start_ext -> device
   sdb::Workspace *acquire_ws(hipStream_t stream, bool async) const;

@@ -1,4 +1,6 @@
-// index.hip -- K3 (HBM slab + adjacency loader) and the index's host-side state; the search call itself is
+// index.hip -- K3 (HBM slab + adjacency loader) and the index's host-side state: the device tables and their growth,
+// lifecycle, load / export / compact.  The two graph copies and their transactions are index_versions.hip, the
+// first-stage copy of the rows index_sketch.hip, quantizer code rows index_codes.hip; the search call itself is
 // search_batch.hip, the walk's launcher walk_launch.hip.
 #include <algorithm>
 #include <cmath>
@@ -10,7 +12,6 @@
 #include "bq.h"
 #include "pq.h"
 #include "walk_args.h"
-#include "wave_dist.h"
 
 namespace sdb {
 
@@ -174,6 +175,59 @@ __global__ void k_fill_u32(uint32_t *p, uint32_t v, size_t n) {
   if (i < n) p[i] = v;
 }
 
+// copies n original-layout rows (host or device) into slab rows [first, first+n)
+int store_rows(sdb_index *ix, uint32_t first, uint32_t n, const float *vectors, int mem, hipStream_t stream) {
+  if (n == 0) return SDB_OK;
+  const RowLayout &l = ix->lay;
+  const float *src = vectors;
+  float *staging = nullptr;
+  if (mem == SDB_MEM_HOST) {
+    SDB_HIP(hipMalloc(&staging, (size_t)n * l.dim * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(staging, vectors, (size_t)n * l.dim * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) {
+      (void)hipFree(staging);
+      return fail(SDB_ERR_DEVICE, "H2D copy failed: %s", hipGetErrorString(e));
+    }
+    src = staging;
+  }
+  hipLaunchKernelGGL(k_permute_rows, dim3(n), dim3(128), 0, stream, src, ix->d_slab + (size_t)first * l.ld, n,
+                     l.dim, l.nblk, l.ng, l.tail, l.ld);
+  hipError_t e = hipGetLastError();
+  if (staging) {
+    (void)hipStreamSynchronize(stream);
+    (void)hipFree(staging);
+  }
+  if (e != hipSuccess) return fail(SDB_ERR_DEVICE, "permute launch failed: %s", hipGetErrorString(e));
+  return SDB_OK;
+}
+
+// binaryQuantizer.Set (binary.go:131-139) for slab rows [first, first + n) of an index with a binary quantizer attached
+int encode_bit_rows(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream) {
+  return bq_encode_slab(ix->bq->d_thr, ix->lay, ix->d_slab, first, n, reinterpret_cast<uint64_t *>(ix->d_codes), stream);
+}
+
+// original-layout copy of slab rows [first, first+n) into dst (device)
+int unpermute_rows(const sdb_index *ix, uint32_t first, uint32_t n, float *dst, hipStream_t stream) {
+  if (n == 0) return SDB_OK;
+  const RowLayout &l = ix->lay;
+  hipLaunchKernelGGL(k_unpermute_rows, dim3(n), dim3(128), 0, stream, ix->d_slab + (size_t)first * l.ld, dst, n, l.dim,
+                     l.nblk, l.ng, l.ld);
+  SDB_HIP(hipGetLastError());
+  return SDB_OK;
+}
+
+bool index_ids(const uint64_t *ids, size_t n, std::unordered_map<uint64_t, uint32_t> &map, size_t *first_dup) {
+  map.clear();
+  if (first_dup) *first_dup = n;
+  bool dense = n == 0 || ids[0] != 0;  // (a tombstoned first row: id - ids[0] names no row)
+  for (size_t i = 1; i < n && dense; i++) dense = ids[i] == ids[0] + i;
+  if (dense) return true;
+  map.reserve(n * 2);
+  for (size_t i = 0; i < n; i++)
+    if (ids[i] != 0 && !map.emplace(ids[i], (uint32_t)i).second && first_dup && i < *first_dup) *first_dup = i;
+  return false;
+}
+
 }  // namespace sdb
 
 using namespace sdb;
@@ -181,76 +235,75 @@ using namespace sdb;
 // ------------------------------------------------------------------------------------------
 // sdb_index methods
 // ------------------------------------------------------------------------------------------
-int sdb_index::reserve(uint32_t rows) {
-  if (rows <= cap) return SDB_OK;
-  uint32_t ncap = cap ? cap : 1024;
-  while (ncap < rows) ncap = ncap < (1u << 30) ? ncap * 2 : rows;
+std::array<RowTable, RowTable::kCount> sdb_index::row_tables() {
+  using T = RowTable;
+  const size_t adj_row = (size_t)kAdjStride * 4, ac_row = has_adjcodes() ? (size_t)kAdjStride * code_bytes : 0;  // (code_bytes = M; the quantizer itself is borrowed and may be gone when the index is destroyed)
+  return {{
+      // (in the order of RowTable::Id)
+      {(void **)&d_slab, (size_t)lay.ld * sizeof(float), T::kNoFill, T::kRequired},
+      {(void **)&wr.adj, adj_row, 0xFF, T::kRequired},
+      {(void **)&cm.adj, adj_row, 0xFF, T::kRequired},
+      {(void **)&d_deg, sizeof(uint32_t), 0, T::kRequired},
+      {(void **)&d_clean, sizeof(uint32_t), 0, T::kRequired},  // loaded / appended edges are not "clean"
+      {(void **)&wr.ids, sizeof(uint64_t), T::kNoFill, T::kRequired},
+      {(void **)&cm.ids, sizeof(uint64_t), T::kNoFill, T::kRequired},
+      {(void **)&d_dirty, 1, 0, T::kRequired},
+      {(void **)&d_adjdist, adj_row, T::kNoFill, T::kRequired},  // edge-distance cache of the write path (index.h)
+      {(void **)&d_dcount, sizeof(uint32_t), 0, T::kRequired},   // a row without cached distances has d_dcount 0
+      {(void **)&d_codes, code_bytes, T::kNoFill, T::kQuantizer},  // the code rows of a quantized store grow with it
+      // ... and the neighbours' code rows behind both adjacency copies.  2 x 64 M bytes per row: 41 GB at 10M rows and
+      // M = 32, more than the vectors of d = 768.  A table that grows past the room for them drops them instead of
+      // failing the insert -- the index works without (searches gather code rows by slot)
+      {(void **)&wr.adjcodes, ac_row, T::kNoFill, T::kCache},
+      {(void **)&cm.adjcodes, ac_row, T::kNoFill, T::kCache},
+  }};
+}
+
+int sdb_index::alloc_row_tables(uint32_t rows, FreshBufs &fresh, std::array<void *, RowTable::kCount> &t, bool may_drop_sketch) {
+  const auto tabs = row_tables();
   // every new buffer first; if one allocation fails the ones before it are returned and the index is as it was
-  struct Fresh {
-    std::vector<void *> p;
-    bool keep = false;
-    ~Fresh() {
-      if (!keep)
-        for (void *x : p)
-          if (x) (void)hipFree(x);
-    }
-    int get(void **out, size_t bytes) {
-      SDB_HIP(hipMalloc(out, bytes));
-      p.push_back(*out);
-      return SDB_OK;
-    }
-    // two buffers of a CACHE (the neighbours' code rows behind both adjacency copies): both or neither, and no room
-    // for them is no error -- the index works without (searches gather code rows by slot)
-    bool get_pair_if_room(void **a, void **b, size_t bytes) {
-      *a = *b = nullptr;
-      if (hipMalloc(a, bytes) == hipSuccess && hipMalloc(b, bytes) == hipSuccess) {
-        p.push_back(*a), p.push_back(*b);
-        return true;
-      }
-      (void)hipGetLastError();
-      if (*a) (void)hipFree(*a);
-      *a = *b = nullptr;
-      return false;
-    }
-  } fresh;
-  float *nslab = nullptr, *nad = nullptr;
-  uint32_t *nadj = nullptr, *nradj = nullptr, *ndeg = nullptr, *nclean = nullptr, *ndc = nullptr;
-  uint64_t *nids = nullptr, *nrids = nullptr;
-  uint8_t *ndirty = nullptr, *ncodes = nullptr;
-  std::unique_lock<std::mutex> sg(sketch_mu);  // the knob waits until the float16 copy has followed the growth
   auto get_required = [&]() -> int {
-    SDB_TRY(fresh.get((void **)&nslab, (size_t)ncap * lay.ld * sizeof(float)));
-    SDB_TRY(fresh.get((void **)&nadj, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
-    SDB_TRY(fresh.get((void **)&nradj, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
-    SDB_TRY(fresh.get((void **)&ndeg, (size_t)ncap * sizeof(uint32_t)));
-    SDB_TRY(fresh.get((void **)&nclean, (size_t)ncap * sizeof(uint32_t)));
-    SDB_TRY(fresh.get((void **)&nids, (size_t)ncap * sizeof(uint64_t)));
-    SDB_TRY(fresh.get((void **)&nrids, (size_t)ncap * sizeof(uint64_t)));
-    SDB_TRY(fresh.get((void **)&ndirty, (size_t)ncap));
-    SDB_TRY(fresh.get((void **)&nad, (size_t)ncap * kAdjStride * sizeof(float)));  // edge-distance cache of the write path (index.h)
-    SDB_TRY(fresh.get((void **)&ndc, (size_t)ncap * sizeof(uint32_t)));
-    if (code_bytes) SDB_TRY(fresh.get((void **)&ncodes, (size_t)ncap * code_bytes));  // the code rows of a quantized store grow with it
+    t.fill(nullptr);
+    for (int i = 0; i < RowTable::kCount; i++)
+      if (tabs[i].kind != RowTable::kCache && tabs[i].row_bytes) SDB_TRY(fresh.get_bytes(&t[i], (size_t)rows * tabs[i].row_bytes));
     return SDB_OK;
   };
   if (int rc = get_required()) {
-    if (!d_sketch) return rc;
+    if (!may_drop_sketch || !d_sketch) return rc;
     // a required buffer never goes without for the float16 copy's sake (a cache): drop it and try once more
     (void)hipGetLastError();
-    for (void *x : fresh.p)
-      if (x) (void)hipFree(x);
-    fresh.p.clear();
+    fresh.drop();
     {
       std::unique_lock<sdb::ViewMutex> wl(view_mu);
       drop_sketch();
     }
     SDB_TRY(get_required());
   }
-  uint8_t *nacw = nullptr, *nacr = nullptr;  // ... and the neighbours' code rows behind both adjacency copies
-  const bool had_ac = has_adjcodes();
-  size_t ac_row = had_ac ? (size_t)kAdjStride * pq->M : 0;
-  // (2 x 64 M bytes per row: 41 GB at 10M rows and M = 32, more than the vectors of d = 768.  A table that grows past
-  // the room for them drops them instead of failing the insert -- alloc_adjcodes treats them as optional the same way)
-  if (ac_row && !fresh.get_pair_if_room((void **)&nacw, (void **)&nacr, (size_t)ncap * ac_row)) ac_row = 0;
+  if (const size_t ac_row = tabs[RowTable::kWrAdjCodes].row_bytes)
+    (void)fresh.get_pair_if_room(&t[RowTable::kWrAdjCodes], &t[RowTable::kCmAdjCodes], (size_t)rows * ac_row);
+  for (int i = 0; i < RowTable::kCount; i++)
+    if (t[i] && tabs[i].fill != RowTable::kNoFill) SDB_HIP(hipMemset(t[i], tabs[i].fill, (size_t)rows * tabs[i].row_bytes));
+  return SDB_OK;
+}
+
+void sdb_index::adopt_row_tables(FreshBufs &fresh, const std::array<void *, RowTable::kCount> &t) {
+  const auto tabs = row_tables();
+  for (int i = 0; i < RowTable::kCount; i++) {
+    if (!tabs[i].row_bytes) continue;
+    if (*tabs[i].slot) (void)hipFree(*tabs[i].slot);
+    *tabs[i].slot = t[i];  // (NULL: a cache there was no room for is dropped)
+  }
+  fresh.keep();
+}
+
+int sdb_index::reserve(uint32_t rows) {
+  if (rows <= cap) return SDB_OK;
+  uint32_t ncap = cap ? cap : std::min<uint32_t>(rows, 1024);  // (a first capacity below 1024 is honoured; above, doubled up from 1024)
+  while (ncap < rows) ncap = ncap < (1u << 30) ? ncap * 2 : rows;
+  FreshBufs fresh;
+  std::array<void *, RowTable::kCount> t;
+  std::unique_lock<std::mutex> sg(sketch_mu);  // the knob waits until the float16 copy has followed the growth
+  SDB_TRY(alloc_row_tables(ncap, fresh, t, true));
   // the float16 copy grows with the slab, best-effort under the headroom rule: rows do not move, so it stays current and
   // the next commit converts only the rows it appends (without room the copy keeps covering the rows it has).  Chosen
   // order: a table that already serves from the copy keeps it through growth, so on a device near capacity a bulk
@@ -260,6 +313,7 @@ int sdb_index::reserve(uint32_t rows) {
   void *nsk = nullptr;
   float *nskn = nullptr;
   if (sk_keep && sketch_cap < ncap) {
+    fresh.p.reserve(fresh.p.size() + 2);
     // (the int8 copy: rows of ld bytes and no per-row floats)
     const size_t rows_b = (size_t)ncap * sketch_row_bytes(sketch8), norm_b = sketch8 ? 0 : (size_t)ncap * sizeof(float);
     const uint32_t have = std::min(n, sketch_cap);
@@ -277,46 +331,17 @@ int sdb_index::reserve(uint32_t rows) {
   }
   // the old buffers are freed below: nothing may still be walking them (searches run on streams of their own)
   if (cap) SDB_HIP(hipDeviceSynchronize());
-  SDB_HIP(hipMemset(nadj, 0xFF, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
-  SDB_HIP(hipMemset(nradj, 0xFF, (size_t)ncap * kAdjStride * sizeof(uint32_t)));
-  SDB_HIP(hipMemset(ndeg, 0, (size_t)ncap * sizeof(uint32_t)));
-  SDB_HIP(hipMemset(nclean, 0, (size_t)ncap * sizeof(uint32_t)));  // loaded / appended edges are not "clean"
-  SDB_HIP(hipMemset(ndirty, 0, (size_t)ncap));
   if (n) {
-    SDB_HIP(hipMemcpy(nslab, d_slab, (size_t)n * lay.ld * sizeof(float), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(nadj, d_adj, (size_t)n * kAdjStride * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(nradj, r_adj, (size_t)n * kAdjStride * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(ndeg, d_deg, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(nclean, d_clean, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(nids, d_ids, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(nrids, r_ids, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(ndirty, d_dirty, (size_t)n, hipMemcpyDeviceToDevice));
-  }
-  SDB_HIP(hipMemset(ndc, 0, (size_t)ncap * sizeof(uint32_t)));  // a row without cached distances has d_dcount 0
-  if (n) {
-    SDB_HIP(hipMemcpy(nad, d_adjdist, (size_t)n * kAdjStride * sizeof(float), hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(ndc, d_dcount, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    if (code_bytes) SDB_HIP(hipMemcpy(ncodes, d_codes, (size_t)n * code_bytes, hipMemcpyDeviceToDevice));
-    if (ac_row) {
-      SDB_HIP(hipMemcpy(nacw, d_adjcodes, (size_t)n * ac_row, hipMemcpyDeviceToDevice));
-      SDB_HIP(hipMemcpy(nacr, r_adjcodes, (size_t)n * ac_row, hipMemcpyDeviceToDevice));
-    }
+    const auto tabs = row_tables();
+    for (int i = 0; i < RowTable::kCount; i++)
+      if (t[i]) SDB_HIP(hipMemcpy(t[i], *tabs[i].slot, (size_t)n * tabs[i].row_bytes, hipMemcpyDeviceToDevice));
   }
   SDB_HIP(hipDeviceSynchronize());
   {
     std::unique_lock<sdb::ViewMutex> wl(view_mu);  // searches pick their pointers up under this lock
-    for (void *p : {(void *)d_slab, (void *)d_adj, (void *)r_adj, (void *)d_deg, (void *)d_clean, (void *)d_ids,
-                    (void *)r_ids, (void *)d_dirty, (void *)d_adjdist, (void *)d_dcount})
-      if (p) (void)hipFree(p);
-    if (code_bytes && d_codes) (void)hipFree(d_codes);
-    if (had_ac) (void)hipFree(d_adjcodes), (void)hipFree(r_adjcodes), d_adjcodes = nacw, r_adjcodes = nacr;  // (NULL: dropped)
-    d_slab = nslab, d_adj = nadj, r_adj = nradj, d_deg = ndeg, d_clean = nclean, d_ids = nids, r_ids = nrids;
-    d_dirty = ndirty, d_adjdist = nad, d_dcount = ndc;
-    if (code_bytes) d_codes = ncodes;
-    fresh.keep = true;
+    adopt_row_tables(fresh, t);
     cap = ncap;
-    view.adj = r_adj, view.ids = r_ids, view.adj_codes = r_adjcodes;
-    view_gen++;
+    publish_pointers();  // (growth happens inside open transactions: view.n and the transaction stay)
     if (nsk) {
       (void)hipFree(d_sketch);
       if (d_sketch_norm) (void)hipFree(d_sketch_norm);
@@ -325,304 +350,6 @@ int sdb_index::reserve(uint32_t rows) {
     if (sk_keep) sketch_gen = view_gen;
   }
   return SDB_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// graph versions
-// ------------------------------------------------------------------------------------------
-namespace sdb {
-// rows the transaction wrote (dirty flags) and rows it appended: committed copy -> the writer's stale copy; with the
-// neighbours' code rows behind them (index.h d_adjcodes; code_bytes = 64 M per row, 0: none)
-__global__ void k_sync_rows(const uint32_t *__restrict__ src_adj, uint32_t *__restrict__ dst_adj,
-                            const uint64_t *__restrict__ src_ids, uint64_t *__restrict__ dst_ids,
-                            uint8_t *__restrict__ dirty, uint32_t n, uint32_t first_new,
-                            const uint8_t *__restrict__ src_codes, uint8_t *__restrict__ dst_codes, uint32_t code_bytes) {
-  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  if (row < first_new && !dirty[row]) return;
-  dst_adj[(size_t)row * kAdjStride + lane] = src_adj[(size_t)row * kAdjStride + lane];
-  if (code_bytes) {  // a multiple of 64: whole words when M is a multiple of four, bytes otherwise
-    if ((code_bytes & 255u) == 0) {
-      const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src_codes + (size_t)row * code_bytes);
-      uint32_t *d4 = reinterpret_cast<uint32_t *>(dst_codes + (size_t)row * code_bytes);
-      for (uint32_t i = lane; i < code_bytes / 4; i += 64) d4[i] = s4[i];
-    } else {
-      for (uint32_t i = lane; i < code_bytes; i += 64) dst_codes[(size_t)row * code_bytes + i] = src_codes[(size_t)row * code_bytes + i];
-    }
-  }
-  if (lane == 0) dst_ids[row] = src_ids[row], dirty[row] = 0;
-}
-// The neighbours' code rows behind the adjacency rows (index.h d_adjcodes): out[row][e] = codes[adj[row][e]], zeros behind
-// the edges.  dirty != NULL: only the rows a transaction wrote or appended (first_new: rows at its start).
-__global__ __launch_bounds__(256) void k_adjcodes_rows(const uint32_t *__restrict__ adj, const uint8_t *__restrict__ codes,
-                                                       uint8_t *__restrict__ out, const uint8_t *__restrict__ dirty, uint32_t n,
-                                                       uint32_t first_new, uint32_t M) {
-  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  if (dirty && row < first_new && !dirty[row]) return;
-  const uint32_t nb = adj[(size_t)row * kAdjStride + lane];
-  const size_t at = ((size_t)row * kAdjStride + lane) * M;
-  if ((M & 7u) == 0) {
-    const uint2 *src = reinterpret_cast<const uint2 *>(codes + (size_t)(nb == kNoSlot ? 0u : nb) * M);
-    uint2 *dst = reinterpret_cast<uint2 *>(out + at);
-    for (uint32_t i = 0; i < M / 8; i++) dst[i] = nb == kNoSlot ? make_uint2(0u, 0u) : src[i];
-  } else {
-    for (uint32_t i = 0; i < M; i++) out[at + i] = nb == kNoSlot ? (uint8_t)0 : codes[(size_t)nb * M + i];
-  }
-}
-// sdb_index_abort_write: the rows the transaction wrote take the committed copy back, the rows it appended become
-// empty again.  What only the write path keeps per row -- degree, clean prefix, cached edge distances -- is rebuilt
-// conservatively: the degree from the row, no clean prefix, no cached distances (both only ever save work: a prune
-// that finds none evaluates everything and arrives at the same row, build.hip).
-__global__ void k_restore_rows(const uint32_t *__restrict__ c_adj, uint32_t *__restrict__ w_adj,
-                               const uint64_t *__restrict__ c_ids, uint64_t *__restrict__ w_ids, uint32_t *__restrict__ deg,
-                               uint32_t *__restrict__ clean, uint32_t *__restrict__ dcount, uint8_t *__restrict__ dirty,
-                               uint32_t n_now, uint32_t n_committed) {
-  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n_now) return;
-  const bool appended = row >= n_committed;
-  if (!appended && !dirty[row]) return;
-  const uint32_t e = appended ? kNoSlot : c_adj[(size_t)row * kAdjStride + lane];
-  w_adj[(size_t)row * kAdjStride + lane] = e;
-  const uint32_t d = (uint32_t)__popcll(__ballot(e != kNoSlot));
-  if (lane == 0) {
-    w_ids[row] = appended ? 0ull : c_ids[row];
-    deg[row] = d, clean[row] = 0, dcount[row] = 0, dirty[row] = 0;
-  }
-}
-// test support: rows on which the two copies differ
-__global__ void k_count_version_diff(const uint32_t *a_adj, const uint32_t *b_adj, const uint64_t *a_ids,
-                                     const uint64_t *b_ids, uint32_t n, unsigned long long *out) {
-  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const bool diff = a_adj[(size_t)row * kAdjStride + lane] != b_adj[(size_t)row * kAdjStride + lane] ||
-                    (lane == 0 && a_ids[row] != b_ids[row]);
-  if (__ballot(diff) && lane == 0) atomicAdd(out, 1ull);
-}
-}  // namespace sdb
-
-int sdb_index::begin_write() {
-  if (!in_tx) in_tx = true, tx_n0 = n, tx_dead0 = n_dead, tx_max_id0 = max_node_id, tx_dirty = false;
-  return SDB_OK;
-}
-
-// ---- the float16 copy of the slab (two-precision hop) ----------------------------------------------------------
-namespace sdb {
-// one wave per row: element t of the row -> half t of the copy (sk_half: round to nearest, no denormals), and the
-// row's ||y - y16||, ||y16|| into the table-wide maxima (non-negative floats order like their bit patterns; a NaN's
-// pattern is above every number's, so a row with a NaN makes the bound NaN and the stage discards nothing)
-__global__ __launch_bounds__(256) void k_sketch_rows(const float *__restrict__ slab, uint16_t *__restrict__ sk,
-                                                      float *__restrict__ sk_norm, uint32_t n, uint32_t ld,
-                                                      uint32_t *__restrict__ stats) {
-  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float *s = slab + (size_t)row * ld;
-  uint16_t *d = sk + (size_t)row * ld;
-  double e2 = 0.0, n2 = 0.0;
-  for (uint32_t t = lane; t < ld; t += 64) {
-    const float v = s[t];
-    const _Float16 h = sk_half(v);
-    d[t] = __builtin_bit_cast(uint16_t, h);
-    const double dv = (double)v - (double)(float)h, hv = (double)(float)h;
-    e2 += dv * dv, n2 += hv * hv;
-  }
-  for (int o = 32; o; o >>= 1) e2 += __shfl_xor(e2, o), n2 += __shfl_xor(n2, o);
-  if (lane == 0) {
-    sk_norm[row] = (float)n2;  // ||y16||^2 (the sum in double: one rounding)
-    const float e = (float)(sqrt(e2) * 1.0001), y = (float)(sqrt(n2) * 1.0001);  // rounded up past their own rounding
-    atomicMax(stats, __float_as_uint(e < 0.0f ? 0.0f : e));
-    atomicMax(stats + 1, __float_as_uint(y < 0.0f ? 0.0f : y));
-  }
-}
-
-// ---- the int8 copy (SDB_TUNE_SKETCH = 3, 4; walk_stage.h Int8Rows) ----
-// the largest |element| of `count` floats into *out (a NaN's pattern is above every number's)
-__global__ __launch_bounds__(256) void k_sketch8_absmax(const float *__restrict__ v, size_t count, uint32_t *__restrict__ out) {
-  uint32_t m = 0;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
-    const uint32_t b = __float_as_uint(fabsf(v[i]));
-    m = b > m ? b : m;
-  }
-  for (int o = 32; o; o >>= 1) {
-    const uint32_t x = (uint32_t)__shfl_xor((int)m, o);
-    m = x > m ? x : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-// one wave per row: y8 = clamp(rint(y / s), -127, 127) (s == 0, a table of zeros: 0), element 128 g + 4 L + k of the row at
-// byte 4 ng L + 4 g + k of the copy's (a lane of the walk reads its 4 ng bytes with one load); the row's ||y - s y8|| and
-// ||s y8||, measured in double and rounded up, into the table-wide maxima stats[0], stats[1], and its error relative to its
-// own norm into stats[3] (rows of zeros have none).  A NaN or Inf in a row makes its figures NaN or infinite, and the
-// maxima with them: the stage then discards nothing (and the table fails kSketch8MaxRatio).
-__global__ __launch_bounds__(256) void k_sketch8_rows(const float *__restrict__ slab, uint8_t *__restrict__ sk, uint32_t n,
-                                                       uint32_t ld, uint32_t ng, float scale, uint32_t *__restrict__ stats) {
-  const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float *s = slab + (size_t)row * ld;
-  uint8_t *d = sk + (size_t)row * ld;
-  double e2 = 0.0, n2 = 0.0, y2 = 0.0;
-  for (uint32_t t = lane; t < ld; t += 64) {
-    const float v = s[t];
-    const float f = scale != 0.0f ? fminf(fmaxf(__builtin_rintf(__fdiv_rn(v, scale)), -127.0f), 127.0f) : 0.0f;
-    const uint32_t g = t >> 7, r = t & 127u;
-    d[(r >> 2) * 4 * ng + g * 4 + (r & 3u)] = (uint8_t)(int8_t)(int)f;
-    const double hv = (double)scale * (double)f, dv = (double)v - hv;
-    e2 += dv * dv, n2 += hv * hv, y2 += (double)v * (double)v;
-  }
-  for (int o = 32; o; o >>= 1) e2 += __shfl_xor(e2, o), n2 += __shfl_xor(n2, o), y2 += __shfl_xor(y2, o);
-  if (lane == 0) {
-    const float e = (float)(sqrt(e2) * 1.0001), y = (float)(sqrt(n2) * 1.0001);  // rounded up past their own rounding
-    atomicMax(stats, __float_as_uint(e < 0.0f ? 0.0f : e));
-    atomicMax(stats + 1, __float_as_uint(y < 0.0f ? 0.0f : y));
-    if (!(y2 == 0.0)) {
-      const float rel = (float)(sqrt(e2 / y2) * 1.0001);
-      atomicMax(stats + 3, __float_as_uint(rel < 0.0f ? 0.0f : rel));
-    }
-  }
-}
-}  // namespace sdb
-
-bool sdb_index::sketch8_supported() const {
-  return sketch_supported() && stage_int8((int)lay.ng, P.metric == SDB_METRIC_EUCLIDEAN, false);
-}
-
-bool sdb_index::sketch_supported() const {
-  if (lay.tail != 0 || pq || bq) return false;
-  return stage_shape((int)lay.ng);
-}
-
-bool sdb_index::sketch_room(size_t bytes) {
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return free_b >= bytes + std::max<size_t>((size_t)4 << 30, total_b / 16);
-}
-
-void sdb_index::drop_sketch() {
-  if (d_sketch || d_sketch_norm) (void)hipDeviceSynchronize();  // walks of earlier views may still read it
-  if (d_sketch) (void)hipFree(d_sketch);
-  if (d_sketch_norm) (void)hipFree(d_sketch_norm);
-  d_sketch = nullptr, d_sketch_norm = nullptr, sketch_cap = 0, sketch_gen = 0, sketch8 = false;
-}
-
-// `from` > 0: the copy is current for rows [0, from) -- a Vamana table never rewrites a committed row, it appends
-// (updates are delete + insert, vamana.go:170-251) -- and only the rows behind them are converted; the two maxima
-// carry on from their values (they stay upper bounds when rows are deleted).  Pointers, capacity, maxima and the
-// generation change under the exclusive view lock; the conversion runs outside it when the caller does not hold it
-// (commit: searches of the new view go on reading float32 rows until sketch_gen names it).  Rows below `from` are
-// not written, so the walks of the previous view that still read them are undisturbed.
-void sdb_index::build_sketch(hipStream_t stream, uint32_t from, bool locked) {
-  std::unique_lock<std::mutex> sg(sketch_mu, std::defer_lock);
-  std::unique_lock<sdb::ViewMutex> wl(view_mu, std::defer_lock);
-  if (!locked) sg.lock(), wl.lock();
-  if (!tune_sketch || !sketch_supported()) {  // off, or a table the walk cannot take it for: no memory held for it
-    drop_sketch();
-    return;
-  }
-  // SDB_TUNE_SKETCH = 3, 4: the int8 copy where the table has that stage; a table whose rows fail kSketch8MaxRatio (now, or
-  // with the rows a later commit appends) frees it and takes the float16 copy from then on
-  if (build_sketch_kind(stream, from, locked, wl, sketch8_wanted()) == 2) {
-    sketch8_refused = true;
-    drop_sketch();
-    (void)build_sketch_kind(stream, 0, locked, wl, false);
-  }
-}
-
-int sdb_index::build_sketch_kind(hipStream_t stream, uint32_t from, bool locked, std::unique_lock<sdb::ViewMutex> &wl, bool int8) {
-  if (d_sketch && sketch8 != int8) drop_sketch();  // the other kind of copy (the knob moved between 1 / 2 and 3 / 4): never both
-  const bool carry = from > 0 && from <= n && d_sketch && sketch_cap >= n && sketch_gen != 0;
-  if (!carry) from = 0;
-  sketch_gen = 0;
-  if (n == 0) return 0;
-  const bool reused = d_sketch != nullptr;
-  if (sketch_cap < n) {
-    drop_sketch();
-    const size_t rows = (size_t)cap * sketch_row_bytes(int8), norms = int8 ? 0 : (size_t)cap * sizeof(float);
-    // a cache: without room for it (the rule of build.hip's pair cache) the walk reads float32 rows
-    if (!sketch_room(rows + norms) || hipMalloc(&d_sketch, rows) != hipSuccess || (norms && hipMalloc(&d_sketch_norm, norms) != hipSuccess)) {
-      (void)hipGetLastError();  // (a failed hipMalloc of this cache)
-      drop_sketch();
-      return 1;
-    }
-    sketch_cap = cap, sketch8 = int8;
-  }
-  if (!d_sk_counters) {
-    if (hipMalloc(&d_sk_counters, 4 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(d_sk_counters, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {  // (the copy is optional: so is this)
-      (void)hipGetLastError();  // (a failed allocation or memset of this cache)
-      if (d_sk_counters) (void)hipFree(d_sk_counters);
-      d_sk_counters = nullptr;
-      drop_sketch();
-      return 1;
-    }
-  }
-  void *const sk = d_sketch;
-  float *const sk_norm = d_sketch_norm;
-  uint32_t *stats = reinterpret_cast<uint32_t *>(d_sk_counters + 2);  // four words: the two maxima; int8: + the new rows' largest |element|, the largest relative row error
-  uint32_t h[4] = {0, 0, 0, 0};
-  if (from) memcpy(&h[0], &sk_emax, 4), memcpy(&h[1], &sk_ymax, 4), memcpy(&h[3], &sk8_rel, 4);
-  const uint32_t rows = n, ld = lay.ld, ng = lay.ng;
-  const float *slab = d_slab;
-  float scale = sk8_scale, amax = sk8_amax;
-  bool ok = true;
-  if (int8) {
-    // The scale: appended rows inside the table's range take the scale the copy has; rows beyond it (and a first build)
-    // set a new one from the largest |element| of ALL rows, and every row is converted again -- one pass over the slab.
-    // Walks of the previous view may still read the copy they were given: they finish before a row of it is rewritten.
-    float newmax = 0.0f;
-    ok = hipMemcpyAsync(stats, h, 16, hipMemcpyHostToDevice, stream) == hipSuccess;
-    if (ok && rows > from) {
-      const size_t count = (size_t)(rows - from) * ld;
-      hipLaunchKernelGGL(sdb::k_sketch8_absmax, dim3((uint32_t)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0, stream,
-                         slab + (size_t)from * ld, count, stats + 2);
-      ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && hipMemcpyAsync(&newmax, stats + 2, 4, hipMemcpyDeviceToHost, stream) == hipSuccess;
-    ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-    if (ok && !(from && newmax <= amax)) {  // (a NaN among the new rows: not inside any range)
-      amax = (!from || newmax > amax || newmax != newmax) ? newmax : amax;
-      const float s0 = amax / 127.0f;
-      scale = (s0 > 0.0f && s0 < 3.0e38f) ? nextafterf(s0, 3.4e38f) : s0;  // rounded up; 0 (a table of zeros), Inf and NaN as they are
-      from = 0, h[0] = h[1] = h[3] = 0;
-      if (reused) ok = hipDeviceSynchronize() == hipSuccess;
-    }
-  }
-  if (!locked) wl.unlock();  // (sketch_mu stays held: the knob cannot free the copy under the kernel)
-  ok = ok && hipMemcpyAsync(stats, h, 16, hipMemcpyHostToDevice, stream) == hipSuccess;
-  if (ok && rows > from) {
-    if (int8)
-      hipLaunchKernelGGL(sdb::k_sketch8_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
-                         static_cast<uint8_t *>(sk) + (size_t)from * ld, rows - from, ld, ng, scale, stats);
-    else
-      hipLaunchKernelGGL(sdb::k_sketch_rows, dim3((rows - from + 3) / 4), dim3(256), 0, stream, slab + (size_t)from * ld,
-                         static_cast<uint16_t *>(sk) + (size_t)from * ld, sk_norm + from, rows - from, ld, stats);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  ok = ok && hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, stream) == hipSuccess;
-  ok = hipStreamSynchronize(stream) == hipSuccess && ok;
-  if (!locked) wl.lock();
-  if (!ok) {  // best-effort: the write this follows has been published; its searches read float32 rows
-    (void)hipGetLastError();
-    drop_sketch();
-    return 1;
-  }
-  if (int8) {
-    float e, y, rel;
-    memcpy(&e, &h[0], 4), memcpy(&y, &h[1], 4), memcpy(&rel, &h[3], 4);
-    if (!(e <= kSketch8MaxRatio * y) || !(rel <= kSketch8MaxRatio)) return 2;  // (NaN and Inf included)
-    sk8_scale = scale, sk8_amax = amax, sk8_rel = rel;
-  }
-  memcpy(&sk_emax, &h[0], 4), memcpy(&sk_ymax, &h[1], 4);
-  sketch_gen = view_gen;
-  return 0;
 }
 
 int sdb_index::ensure_idmap(const View &vw, hipStream_t stream) const {
@@ -652,177 +379,6 @@ int sdb_index::ensure_idmap(const View &vw, hipStream_t stream) const {
   SDB_HIP(hipGetLastError());
   SDB_HIP(hipStreamSynchronize(stream));  // other searches probe it from their own streams
   idmap.gen = view_gen;
-  return SDB_OK;
-}
-
-int sdb_index::alloc_adjcodes() {
-  if (d_adjcodes) (void)hipFree(d_adjcodes);
-  if (r_adjcodes) (void)hipFree(r_adjcodes);
-  d_adjcodes = r_adjcodes = nullptr;
-  view.adj_codes = nullptr;
-  if (!pq || pq->M > kAdjCodesMaxM) return SDB_OK;
-  const size_t bytes = (size_t)cap * kAdjStride * pq->M;
-  // a cache of what the code rows hold: without room for it the walk gathers by slot, as it does for larger M
-  if (hipMalloc(&d_adjcodes, bytes) != hipSuccess || hipMalloc(&r_adjcodes, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    if (d_adjcodes) (void)hipFree(d_adjcodes);
-    d_adjcodes = r_adjcodes = nullptr;
-  }
-  return SDB_OK;
-}
-
-int sdb_index::rebuild_adjcodes(hipStream_t stream) {
-  if (!has_adjcodes()) return SDB_OK;
-  const uint32_t M = pq->M;
-  if (n) hipLaunchKernelGGL(sdb::k_adjcodes_rows, dim3((n + 3) / 4), dim3(256), 0, stream, d_adj, d_codes, d_adjcodes, nullptr, n, 0u, M);
-  if (view.n)
-    hipLaunchKernelGGL(sdb::k_adjcodes_rows, dim3((view.n + 3) / 4), dim3(256), 0, stream, r_adj, d_codes, r_adjcodes, nullptr, view.n,
-                       0u, M);
-  SDB_HIP(hipGetLastError());
-  SDB_HIP(hipStreamSynchronize(stream));
-  view.adj_codes = r_adjcodes;
-  return SDB_OK;
-}
-
-int sdb_index::commit(hipStream_t stream) {
-  if (!in_tx) return SDB_OK;
-  const bool sk_current = sketch_current();  // the float16 copy describes the rows below tx_n0
-  const uint32_t need = (uint32_t)((h_start_ext.size() + 63) / 64 * 64);
-  const uint32_t ac_bytes = has_adjcodes() ? kAdjStride * pq->M : 0;
-  if (ac_bytes && n) {
-    // the writer's copy of the neighbours' code rows catches up with what the transaction did to the adjacency rows --
-    // before the copies change hands, while the searches still walk the other one
-    hipLaunchKernelGGL(sdb::k_adjcodes_rows, dim3((n + 3) / 4), dim3(256), 0, stream, d_adj, d_codes, d_adjcodes, d_dirty, n,
-                       tx_n0 < n ? tx_n0 : n, pq->M);
-    SDB_HIP(hipGetLastError());
-    SDB_HIP(hipStreamSynchronize(stream));
-  }
-  {
-    std::unique_lock<sdb::ViewMutex> wl(view_mu);
-    // every search that took the old view has enqueued its kernels and recorded its event by now (it held the
-    // shared lock until then): the writer's stream waits for them before it touches the copy they walk
-    {
-      std::lock_guard<std::mutex> g(mu);
-      for (auto *w : pool)
-        if (w->launched_valid) SDB_HIP(hipStreamWaitEvent(stream, w->launched, 0));
-    }
-    std::swap(d_adj, r_adj);
-    std::swap(d_adjcodes, r_adjcodes);
-    std::swap(d_ids, r_ids);
-    std::swap(d_start_ext, r_start_ext);
-    std::swap(start_ext_cap, r_start_ext_cap);
-    view.n = n, view.adj = r_adj, view.ids = r_ids, view.start_ext = r_start_ext;
-    view.start_ext_n = (uint32_t)h_start_ext.size();
-    view.adj_codes = r_adjcodes;
-    view_gen++;
-    tx_deleted.clear();
-    in_tx = false, tx_explicit = false, tx_dirty = false;
-  }
-  // the writer's copy is now the one the last version's searches walked: bring it up to date
-  if (n) {
-    hipLaunchKernelGGL(sdb::k_sync_rows, dim3((n + 3) / 4), dim3(256), 0, stream, r_adj, d_adj, r_ids, d_ids, d_dirty, n,
-                       tx_n0 < n ? tx_n0 : n, r_adjcodes, d_adjcodes, ac_bytes);
-    SDB_HIP(hipGetLastError());
-  }
-  if (need) {
-    if (need > start_ext_cap) {
-      SDB_HIP(hipStreamSynchronize(stream));
-      if (d_start_ext) (void)hipFree(d_start_ext);
-      d_start_ext = nullptr, start_ext_cap = 0;
-      SDB_HIP(hipMalloc(&d_start_ext, (size_t)need * 2 * 4));
-      start_ext_cap = need * 2;
-    }
-    SDB_HIP(hipMemcpyAsync(d_start_ext, r_start_ext, (size_t)need * 4, hipMemcpyDeviceToDevice, stream));
-  }
-  // the float16 copy follows: on `stream`, which has waited for the searches of the old view (above); searches of the
-  // new one read float32 rows until sketch_gen says the copy is theirs.  Best-effort: the write is published already.
-  build_sketch(stream, sk_current && start_slot >= 0 ? tx_n0 : 0, false);
-  return SDB_OK;
-}
-
-int sdb_index::rollback() {
-  std::unique_lock<sdb::ViewMutex> wl(view_mu);  // searches translate filter ids with the tables changed below
-  SDB_HIP(hipDeviceSynchronize());               // the transaction's kernels are done
-  if (n)
-    hipLaunchKernelGGL(sdb::k_restore_rows, dim3((n + 3) / 4), dim3(256), 0, nullptr, r_adj, d_adj, r_ids, d_ids, d_deg,
-                       d_clean, d_dcount, d_dirty, n, tx_n0);
-  SDB_HIP(hipGetLastError());
-  // The writer's copy of the neighbours' code rows follows the restored adjacency rows.  commit() brings it to the
-  // transaction's state BEFORE the copies change hands, so a commit that failed after that step -- or a transaction that
-  // is simply aborted after its rows were written -- would leave restored rows carrying the transaction's code rows:
-  // edge e walked with another node's codes, silently.  All committed rows (a rollback is rare; 64 M bytes per row).
-  if (has_adjcodes() && tx_n0) {
-    hipLaunchKernelGGL(sdb::k_adjcodes_rows, dim3((tx_n0 + 3) / 4), dim3(256), 0, nullptr, d_adj, d_codes, d_adjcodes, nullptr,
-                       tx_n0, 0u, pq->M);
-    SDB_HIP(hipGetLastError());
-  }
-  // the start node's overflow list as committed
-  const uint32_t ext_n = view.start_ext_n, need = (ext_n + 63) / 64 * 64;
-  h_start_ext.assign(ext_n, 0);
-  if (ext_n) {
-    SDB_HIP(hipMemcpy(h_start_ext.data(), r_start_ext, (size_t)ext_n * 4, hipMemcpyDeviceToHost));
-    if (need > start_ext_cap) {
-      if (d_start_ext) (void)hipFree(d_start_ext);
-      d_start_ext = nullptr, start_ext_cap = 0;
-      SDB_HIP(hipMalloc(&d_start_ext, (size_t)need * 2 * 4));
-      start_ext_cap = need * 2;
-    }
-    SDB_HIP(hipMemcpy(d_start_ext, r_start_ext, (size_t)need * 4, hipMemcpyDeviceToDevice));
-  }
-  SDB_HIP(hipDeviceSynchronize());
-  // host tables: appended rows go, rows the transaction tombstoned get their ids back
-  h_ids.resize(tx_n0);
-  for (auto &kv : tx_deleted)
-    if (kv.second < tx_n0) h_ids[kv.second] = kv.first;
-  n = tx_n0, n_dead = tx_dead0, max_node_id = tx_max_id0;
-  bool dense = n > 0;
-  for (uint32_t i = 1; i < n && dense; i++) dense = h_ids[i] == h_ids[0] + i;
-  if (n && h_ids[0] == 0) dense = false;
-  dense_ids = n == 0 ? true : dense;
-  id2slot.clear();
-  if (!dense_ids) {
-    id2slot.reserve((size_t)n * 2);
-    for (uint32_t sl = 0; sl < n; sl++)
-      if (h_ids[sl] != 0) id2slot.emplace(h_ids[sl], sl);
-  }
-  tx_deleted.clear();
-  in_tx = false, tx_explicit = false, tx_dirty = false;
-  // the committed rows are where they were: a current copy still describes them (exclusive lock held, device idle)
-  if (!sketch_current() || sketch_cap < n) build_sketch(nullptr, 0, true);
-  return SDB_OK;
-}
-
-int sdb_index::publish_full() {
-  SDB_HIP(hipDeviceSynchronize());
-  std::unique_lock<sdb::ViewMutex> wl(view_mu);
-  if (n) {
-    SDB_HIP(hipMemcpy(r_adj, d_adj, (size_t)n * kAdjStride * 4, hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemcpy(r_ids, d_ids, (size_t)n * 8, hipMemcpyDeviceToDevice));
-    SDB_HIP(hipMemset(d_dirty, 0, n));
-    if (has_adjcodes()) {
-      hipLaunchKernelGGL(sdb::k_adjcodes_rows, dim3((n + 3) / 4), dim3(256), 0, nullptr, d_adj, d_codes, d_adjcodes, nullptr, n, 0u, pq->M);
-      SDB_HIP(hipGetLastError());
-      SDB_HIP(hipMemcpy(r_adjcodes, d_adjcodes, (size_t)n * kAdjStride * pq->M, hipMemcpyDeviceToDevice));
-    }
-  }
-  const uint32_t need = (uint32_t)((h_start_ext.size() + 63) / 64 * 64);
-  if (need) {
-    if (need > r_start_ext_cap) {
-      if (r_start_ext) (void)hipFree(r_start_ext);
-      r_start_ext = nullptr, r_start_ext_cap = 0;
-      SDB_HIP(hipMalloc(&r_start_ext, (size_t)need * 2 * 4));
-      r_start_ext_cap = need * 2;
-    }
-    SDB_HIP(hipMemcpy(r_start_ext, d_start_ext, (size_t)need * 4, hipMemcpyDeviceToDevice));
-  }
-  view.n = n, view.adj = r_adj, view.ids = r_ids, view.start_ext = r_start_ext;
-  view.start_ext_n = (uint32_t)h_start_ext.size();
-  view.adj_codes = r_adjcodes;
-  view_gen++;
-  tx_deleted.clear();
-  in_tx = false, tx_explicit = false, tx_dirty = false;
-  SDB_HIP(hipDeviceSynchronize());  // searches that slipped in between the first wait and the lock
-  build_sketch(nullptr, 0, true);  // (best-effort: the view is published)
   return SDB_OK;
 }
 
@@ -869,27 +425,6 @@ void sdb_index::release_ws(Workspace *ws, hipStream_t stream, bool async) const 
     }
   }
   ws->busy = false;
-}
-
-// uploads the start node's overflow edges, padded with kNoSlot to whole 64-entry chunks (search_kernel.h reads them
-// like adjacency rows).  Writers are exclusive (the reference holds the shard's write lock), so nothing reads the
-// old buffer once the device is idle.
-int sdb_index::sync_start_ext() {
-  const uint32_t need = (uint32_t)((h_start_ext.size() + 63) / 64 * 64);
-  if (need > start_ext_cap) {
-    SDB_HIP(hipDeviceSynchronize());
-    if (d_start_ext) (void)hipFree(d_start_ext);
-    d_start_ext = nullptr, start_ext_cap = 0;
-    const uint32_t ncap = need * 2;
-    SDB_HIP(hipMalloc(&d_start_ext, (size_t)ncap * 4));
-    start_ext_cap = ncap;
-  }
-  if (need) {
-    std::vector<uint32_t> padded(need, kNoSlot);
-    std::copy(h_start_ext.begin(), h_start_ext.end(), padded.begin());
-    SDB_HIP(hipMemcpy(d_start_ext, padded.data(), (size_t)need * 4, hipMemcpyHostToDevice));
-  }
-  return SDB_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1013,25 +548,14 @@ int sdb_index_destroy(sdb_index *ix) try {
   if (!ix) return SDB_OK;
   DeviceGuard dg(ix->P.device);
   (void)hipDeviceSynchronize();
-  if (ix->d_slab) (void)hipFree(ix->d_slab);
+  for (const RowTable &t : ix->row_tables())
+    if (*t.slot) (void)hipFree(*t.slot);
   ix->drop_sketch();
   if (ix->d_sk_counters) (void)hipFree(ix->d_sk_counters);
-  if (ix->d_adj) (void)hipFree(ix->d_adj);
-  if (ix->d_deg) (void)hipFree(ix->d_deg);
-  if (ix->d_clean) (void)hipFree(ix->d_clean);
-  if (ix->d_adjdist) (void)hipFree(ix->d_adjdist);
-  if (ix->d_dcount) (void)hipFree(ix->d_dcount);
-  if (ix->d_ids) (void)hipFree(ix->d_ids);
-  if (ix->r_adj) (void)hipFree(ix->r_adj);
-  if (ix->r_ids) (void)hipFree(ix->r_ids);
   if (ix->idmap.keys) (void)hipFree(ix->idmap.keys);
   if (ix->idmap.vals) (void)hipFree(ix->idmap.vals);
-  if (ix->r_start_ext) (void)hipFree(ix->r_start_ext);
-  if (ix->d_dirty) (void)hipFree(ix->d_dirty);
-  if (ix->d_start_ext) (void)hipFree(ix->d_start_ext);
-  if (ix->d_codes) (void)hipFree(ix->d_codes);
-  if (ix->d_adjcodes) (void)hipFree(ix->d_adjcodes);
-  if (ix->r_adjcodes) (void)hipFree(ix->r_adjcodes);
+  if (ix->wr.start_ext) (void)hipFree(ix->wr.start_ext);
+  if (ix->cm.start_ext) (void)hipFree(ix->cm.start_ext);
   if (ix->d_bstats) (void)hipFree(ix->d_bstats);
   for (auto e : ix->ev0)
     if (e) (void)hipEventDestroy(e);
@@ -1046,38 +570,6 @@ int sdb_index_destroy(sdb_index *ix) try {
 }
 SDB_API_CATCH("sdb_index_destroy")
 
-// copies n original-layout rows (host or device) into slab rows [first, first+n)
-static int store_rows(sdb_index *ix, uint32_t first, uint32_t n, const float *vectors, int mem, hipStream_t stream);
-static int store_rows(sdb_index *ix, uint32_t first, uint32_t n, const float *vectors, int mem,
-                      hipStream_t stream) {
-  if (n == 0) return SDB_OK;
-  const RowLayout &l = ix->lay;
-  const float *src = vectors;
-  float *staging = nullptr;
-  if (mem == SDB_MEM_HOST) {
-    SDB_HIP(hipMalloc(&staging, (size_t)n * l.dim * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(staging, vectors, (size_t)n * l.dim * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) {
-      (void)hipFree(staging);
-      return fail(SDB_ERR_DEVICE, "H2D copy failed: %s", hipGetErrorString(e));
-    }
-    src = staging;
-  }
-  hipLaunchKernelGGL(k_permute_rows, dim3(n), dim3(128), 0, stream, src, ix->d_slab + (size_t)first * l.ld, n,
-                     l.dim, l.nblk, l.ng, l.tail, l.ld);
-  hipError_t e = hipGetLastError();
-  if (staging) {
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(staging);
-  }
-  if (e != hipSuccess) return fail(SDB_ERR_DEVICE, "permute launch failed: %s", hipGetErrorString(e));
-  return SDB_OK;
-}
-
-// binaryQuantizer.Set (binary.go:131-139) for slab rows [first, first + n) of an index with a binary quantizer attached
-static int encode_bit_rows(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream) {
-  return bq_encode_slab(ix->bq->d_thr, ix->lay, ix->d_slab, first, n, reinterpret_cast<uint64_t *>(ix->d_codes), stream);
-}
 int sdb_index_set_start(sdb_index *ix, const float *vec, int mem) try {
   if (!ix || !vec) return fail(SDB_ERR_INVALID, "NULL argument");
   if (ix->start_slot >= 0) return SDB_OK;  // vamana.go:95-97: already there
@@ -1087,7 +579,7 @@ int sdb_index_set_start(sdb_index *ix, const float *vec, int mem) try {
   SDB_TRY(store_rows(ix, 0, 1, vec, mem, nullptr));
   if (ix->bq) SDB_TRY(encode_bit_rows(ix, 0, 1, nullptr));  // vecStore.Set encodes (binary.go:131-139)
   uint64_t id = SDB_STARTID;
-  SDB_HIP(hipMemcpy(ix->d_ids, &id, sizeof(id), hipMemcpyHostToDevice));
+  SDB_HIP(hipMemcpy(ix->wr.ids, &id, sizeof(id), hipMemcpyHostToDevice));
   SDB_HIP(hipDeviceSynchronize());
   ix->h_ids.assign(1, id);
   ix->dense_ids = true;
@@ -1116,31 +608,26 @@ int sdb_index_load(sdb_index *ix, uint64_t n, const uint64_t *ids, const float *
       ix->n = 0, ix->start_slot = -1, ix->max_node_id = 0, ix->dense_ids = true;
       ix->h_ids.clear(), ix->id2slot.clear(), ix->h_start_ext.clear();
       if (wrote) {
-        (void)hipMemset(ix->d_adj, 0xFF, (size_t)wrote * kAdjStride * 4);
-        (void)hipMemset(ix->d_deg, 0, (size_t)wrote * 4);
+        for (const RowTable &t : ix->row_tables())
+          if (*t.slot && t.fill != RowTable::kNoFill) (void)hipMemset(*t.slot, t.fill, (size_t)wrote * t.row_bytes);
         (void)hipDeviceSynchronize();
       }
     }
   } undo{ix};
   // id table
   ix->h_ids.resize(n);
-  bool dense = true;
-  for (uint64_t i = 0; i < n; i++) {
-    ix->h_ids[i] = ids ? ids[i] : i + 1;
-    if (i && ix->h_ids[i] != ix->h_ids[0] + i) dense = false;
-  }
-  ix->dense_ids = dense;
-  ix->id2slot.clear();
+  for (uint64_t i = 0; i < n; i++) ix->h_ids[i] = ids ? ids[i] : i + 1;
+  size_t dup = n;
+  ix->dense_ids = index_ids(ix->h_ids.data(), n, ix->id2slot, &dup);
   ix->start_slot = -1;
   ix->max_node_id = 0;
-  if (!dense) ix->id2slot.reserve(n * 2);
   for (uint64_t i = 0; i < n; i++) {
     uint64_t id = ix->h_ids[i];
     if (id == 0) {
       ix->h_ids.clear();
       return fail(SDB_ERR_INVALID, "invalid point id: 0");
     }
-    if (!dense && !ix->id2slot.emplace(id, (uint32_t)i).second) {
+    if (i == dup) {
       ix->h_ids.clear();
       return fail(SDB_ERR_INVALID, "duplicate node id %llu", (unsigned long long)id);
     }
@@ -1181,9 +668,9 @@ int sdb_index_load(sdb_index *ix, uint64_t n, const uint64_t *ids, const float *
   }
   SDB_TRY(ix->sync_start_ext());
   undo.wrote = (uint32_t)n;
-  SDB_HIP(hipMemcpy(ix->d_adj, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  SDB_HIP(hipMemcpy(ix->wr.adj, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   SDB_HIP(hipMemcpy(ix->d_deg, deg.data(), deg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  SDB_HIP(hipMemcpy(ix->d_ids, ix->h_ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+  SDB_HIP(hipMemcpy(ix->wr.ids, ix->h_ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
   SDB_TRY(store_rows(ix, 0, (uint32_t)n, vectors, mem, nullptr));
   if (ix->bq) SDB_TRY(encode_bit_rows(ix, 0, (uint32_t)n, nullptr));
   SDB_TRY(ix->publish_full());
@@ -1191,90 +678,6 @@ int sdb_index_load(sdb_index *ix, uint64_t n, const uint64_t *ids, const float *
   return SDB_OK;
 }
 SDB_API_CATCH("sdb_index_load")
-
-// IndexVamana.InsertUpdateDelete is ONE write transaction made of several calls here (inserts, one delete scan,
-// re-inserts of the updated points); the shard runs it under its write lock while searches keep being served --
-// by a cold index built from the bucket when the cached one is locked (shard/cache/manager.go:159-181).  Here the
-// searches simply keep walking the last committed graph: between begin_write and commit every insert_batch /
-// delete_batch changes the writer's copy only.  Without begin_write each such call is a transaction by itself.
-int sdb_index_begin_write(sdb_index *ix) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (ix->broken) return fail(SDB_ERR_STATE, "index is unusable after a failed write; reload it from the bucket");
-  if (ix->in_tx && ix->tx_explicit) return fail(SDB_ERR_STATE, "a write transaction is already open");
-  SDB_TRY(ix->begin_write());
-  ix->tx_explicit = true;
-  return SDB_OK;
-}
-SDB_API_CATCH("sdb_index_begin_write")
-
-int sdb_index_commit(sdb_index *ix, void *stream_) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (!ix->in_tx) return fail(SDB_ERR_STATE, "no write transaction is open");
-  if (ix->broken) return fail(SDB_ERR_STATE, "index is unusable after a failed write; reload it from the bucket");
-  DeviceGuard dg(ix->P.device);
-  hipStream_t stream = as_stream(stream_);
-  SDB_TRY(ix->commit(stream));
-  SDB_HIP(hipStreamSynchronize(stream));
-  return SDB_OK;
-}
-SDB_API_CATCH("sdb_index_commit")
-
-// The way out of a transaction that will not be committed (a host that found a bad point after begin_write, a failed
-// call, a cancelled request).  Searches never saw the transaction: they walk the committed copy of the graph (index.h
-// graph versions), which is exactly what a rollback needs -- the rows the transaction wrote take the committed copy
-// back, the rows it appended are dropped, the host's id tables follow.  The reference has no such thing: after an
-// error inside a transaction its cache manager scraps the shard's cache and rebuilds it from the bucket
-// (shard/cache/manager.go:231-240); here the index is what it was at begin_write, in milliseconds.  Only a handle that
-// a device failure left half-written (index.h `broken`) cannot be brought back.
-int sdb_index_abort_write(sdb_index *ix) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (ix->broken) return fail(SDB_ERR_STATE, "index is unusable after a failed write; reload it from the bucket");
-  if (!ix->in_tx) return SDB_OK;
-  if (!ix->tx_dirty) {  // nothing to undo
-    std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
-    ix->tx_deleted.clear();
-    ix->in_tx = false, ix->tx_explicit = false;
-    return SDB_OK;
-  }
-  DeviceGuard dg(ix->P.device);
-  int rc;
-  try {
-    rc = ix->rollback();
-  } catch (...) {
-    rc = on_exception("sdb_index_abort_write");
-  }
-  if (rc != SDB_OK) ix->broken = true;  // a device error (or no host memory for the id tables) half-way through the restore
-  return rc;
-}
-SDB_API_CATCH("sdb_index_abort_write")
-
-// test support: the number of rows on which the two graph copies differ (0 whenever no transaction is open)
-int sdb_index_version_diff(const sdb_index *ix, uint64_t *rows) try {
-  if (!ix || !rows) return fail(SDB_ERR_INVALID, "NULL argument");
-  *rows = 0;
-  if (ix->n == 0) return SDB_OK;
-  DeviceGuard dg(ix->P.device);
-  unsigned long long *d = nullptr;
-  SDB_HIP(hipMalloc(&d, 8));
-  SDB_HIP(hipMemset(d, 0, 8));
-  SDB_HIP(hipDeviceSynchronize());
-  hipLaunchKernelGGL(k_count_version_diff, dim3((ix->n + 3) / 4), dim3(256), 0, nullptr, ix->d_adj, ix->r_adj, ix->d_ids,
-                     ix->r_ids, ix->n, d);
-  unsigned long long h = 0;
-  hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(SDB_ERR_DEVICE, "version check failed: %s", hipGetErrorString(e));
-  *rows = h;
-  if (ix->h_start_ext.size()) {
-    const size_t m = ix->h_start_ext.size();
-    std::vector<uint32_t> a(m), b(m);
-    SDB_HIP(hipMemcpy(a.data(), ix->d_start_ext, m * 4, hipMemcpyDeviceToHost));
-    SDB_HIP(hipMemcpy(b.data(), ix->r_start_ext, m * 4, hipMemcpyDeviceToHost));
-    if (a != b) *rows += 1;
-  }
-  return SDB_OK;
-}
-SDB_API_CATCH("sdb_index_version_diff")
 
 int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
   if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
@@ -1354,22 +757,6 @@ int sdb_index_set_tuning(sdb_index *ix, int key, uint64_t value) try {
   }
 }
 SDB_API_CATCH("sdb_index_set_tuning")
-
-int sdb_index_sketch_stats(sdb_index *ix, uint64_t out[3]) try {
-  if (!ix || !out) return fail(SDB_ERR_INVALID, "NULL argument");
-  DeviceGuard dg(ix->P.device);
-  out[0] = out[1] = out[2] = 0;
-  std::shared_lock<sdb::ViewMutex> rl(ix->view_mu);
-  if (ix->d_sk_counters) {
-    SDB_HIP(hipDeviceSynchronize());
-    unsigned long long h[2] = {0, 0};
-    SDB_HIP(hipMemcpy(h, ix->d_sk_counters, sizeof(h), hipMemcpyDeviceToHost));
-    out[0] = h[0], out[1] = h[1];
-  }
-  out[2] = (ix->tune_sketch && ix->sketch_current() && !ix->in_tx) ? 1 : 0;
-  return SDB_OK;
-}
-SDB_API_CATCH("sdb_index_sketch_stats")
 
 int sdb_index_build_stats(const sdb_index *ix, uint64_t *out, uint32_t cap) try {
   if (!ix || !out) return fail(SDB_ERR_INVALID, "NULL argument");
@@ -1534,124 +921,58 @@ int sdb_index_compact(sdb_index *ix) try {
     if (ix->h_ids[s] != 0) map[s] = (uint32_t)live.size(), live.push_back(s);
   const uint32_t nn = (uint32_t)live.size();
   // ---- every allocation first: a failure leaves the index as it was
-  struct Bufs {
-    std::vector<void *> p;
-    bool keep = false;
-    ~Bufs() {
-      if (!keep)
-        for (void *x : p)
-          if (x) (void)hipFree(x);
-    }
-    int get(void **out, size_t bytes) {
-      SDB_HIP(hipMalloc(out, bytes));
-      p.push_back(*out);
-      return SDB_OK;
-    }
-  } nb, tmp;
-  float *nslab = nullptr, *nad = nullptr;
-  uint32_t *nadj = nullptr, *nradj = nullptr, *ndeg = nullptr, *nclean = nullptr, *ndc = nullptr;
-  uint64_t *nids = nullptr, *nrids = nullptr;
-  uint8_t *ncodes = nullptr;
+  using T = RowTable;
+  FreshBufs nb, tmp;
+  std::array<void *, T::kCount> t;
+  SDB_TRY(ix->alloc_row_tables(cap, nb, t, false));
+  // (the neighbours' code rows follow the renumbered adjacency; without room for them the compacted index goes on without)
+  const GraphCopy nwr{(uint32_t *)t[T::kWrAdj], (uint64_t *)t[T::kWrIds], nullptr, 0, (uint8_t *)t[T::kWrAdjCodes]};
+  uint8_t *const ncodes = (uint8_t *)t[T::kCodes];
   uint32_t *d_live = nullptr, *d_map = nullptr, *d_lost = nullptr;
-  SDB_TRY(nb.get((void **)&nslab, (size_t)cap * ld * 4));
-  SDB_TRY(nb.get((void **)&nadj, (size_t)cap * kAdjStride * 4));
-  SDB_TRY(nb.get((void **)&nradj, (size_t)cap * kAdjStride * 4));
-  SDB_TRY(nb.get((void **)&nad, (size_t)cap * kAdjStride * 4));
-  SDB_TRY(nb.get((void **)&ndeg, (size_t)cap * 4));
-  SDB_TRY(nb.get((void **)&nclean, (size_t)cap * 4));
-  SDB_TRY(nb.get((void **)&ndc, (size_t)cap * 4));
-  SDB_TRY(nb.get((void **)&nids, (size_t)cap * 8));
-  SDB_TRY(nb.get((void **)&nrids, (size_t)cap * 8));
-  if (M) SDB_TRY(nb.get((void **)&ncodes, (size_t)cap * M));
-  uint8_t *nacw = nullptr, *nacr = nullptr;  // the neighbours' code rows follow the renumbered adjacency
-  const bool had_ac = ix->has_adjcodes();
-  if (had_ac && (hipMalloc((void **)&nacw, (size_t)cap * kAdjStride * M) != hipSuccess ||
-                 hipMalloc((void **)&nacr, (size_t)cap * kAdjStride * M) != hipSuccess)) {
-    // a cache (reserve, alloc_adjcodes): without room for its second copy the compacted index goes on without it
-    (void)hipGetLastError();
-    if (nacw) (void)hipFree(nacw);
-    nacw = nacr = nullptr;
-  }
-  struct AcGuard {  // until they change hands below
-    uint8_t *&a, *&b;
-    bool keep = false;
-    ~AcGuard() {
-      if (!keep) {
-        if (a) (void)hipFree(a);
-        if (b) (void)hipFree(b);
-      }
-    }
-  } ac_guard{nacw, nacr};
-  SDB_TRY(tmp.get((void **)&d_live, (size_t)nn * 4 + 4));
-  SDB_TRY(tmp.get((void **)&d_map, (size_t)n * 4));
-  SDB_TRY(tmp.get((void **)&d_lost, 4));
+  SDB_TRY(tmp.get_n(&d_live, (size_t)nn + 1));
+  SDB_TRY(tmp.get_n(&d_map, n));
+  SDB_TRY(tmp.get_n(&d_lost, 1));
   SDB_HIP(hipMemcpy(d_live, live.data(), (size_t)nn * 4, hipMemcpyHostToDevice));
   SDB_HIP(hipMemcpy(d_map, map.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   SDB_HIP(hipMemset(d_lost, 0, 4));
-  SDB_HIP(hipMemset(nadj, 0xFF, (size_t)cap * kAdjStride * 4));
-  SDB_HIP(hipMemset(ndeg, 0, (size_t)cap * 4));
-  SDB_HIP(hipMemset(nclean, 0, (size_t)cap * 4));
-  SDB_HIP(hipMemset(ndc, 0, (size_t)cap * 4));
-  hipLaunchKernelGGL(k_compact_rows, dim3(nn), dim3(64), 0, nullptr, d_live, d_map, ld, ix->d_slab, nslab, ix->d_adj, nadj,
-                     ix->d_adjdist, nad, ix->d_deg, ndeg, ix->d_clean, nclean, ix->d_dcount, ndc, ix->d_ids, nids,
-                     ix->d_codes, ncodes, M, d_lost);
+  hipLaunchKernelGGL(k_compact_rows, dim3(nn), dim3(64), 0, nullptr, d_live, d_map, ld, ix->d_slab, (float *)t[T::kSlab], ix->wr.adj,
+                     nwr.adj, ix->d_adjdist, (float *)t[T::kAdjDist], ix->d_deg, (uint32_t *)t[T::kDeg], ix->d_clean,
+                     (uint32_t *)t[T::kClean], ix->d_dcount, (uint32_t *)t[T::kDCount], ix->wr.ids, nwr.ids, ix->d_codes, ncodes, M,
+                     d_lost);
   SDB_HIP(hipGetLastError());
-  SDB_HIP(hipMemcpy(nradj, nadj, (size_t)cap * kAdjStride * 4, hipMemcpyDeviceToDevice));
-  SDB_HIP(hipMemcpy(nrids, nids, (size_t)nn * 8, hipMemcpyDeviceToDevice));
-  if (nacw && nn) {
-    hipLaunchKernelGGL(k_adjcodes_rows, dim3((nn + 3) / 4), dim3(256), 0, nullptr, nadj, ncodes, nacw, nullptr, nn, 0u, M);
-    SDB_HIP(hipGetLastError());
-    SDB_HIP(hipMemcpy(nacr, nacw, (size_t)nn * kAdjStride * M, hipMemcpyDeviceToDevice));
+  SDB_HIP(hipMemcpy(t[T::kCmAdj], nwr.adj, (size_t)cap * kAdjStride * 4, hipMemcpyDeviceToDevice));
+  SDB_HIP(hipMemcpy(t[T::kCmIds], nwr.ids, (size_t)nn * 8, hipMemcpyDeviceToDevice));
+  if (nwr.adjcodes && nn) {
+    SDB_TRY(ix->fill_adjcodes(nwr, nn, nullptr, 0, nullptr, ncodes));
+    SDB_HIP(hipMemcpy(t[T::kCmAdjCodes], nwr.adjcodes, (size_t)nn * kAdjStride * M, hipMemcpyDeviceToDevice));
   }
   uint32_t lost = 0;
   SDB_HIP(hipMemcpy(&lost, d_lost, 4, hipMemcpyDeviceToHost));
   if (lost) return fail(SDB_ERR_STATE, "%u edges point at deleted rows: the graph is inconsistent, nothing was changed", lost);
   // the host tables of the compacted index, complete before anything changes hands (their memory may not be there)
   std::vector<uint64_t> h(nn);
-  bool dense = true;
-  for (uint32_t j = 0; j < nn; j++) {
-    h[j] = ix->h_ids[live[j]];
-    if (j && h[j] != h[0] + j) dense = false;
-  }
+  for (uint32_t j = 0; j < nn; j++) h[j] = ix->h_ids[live[j]];
   std::unordered_map<uint64_t, uint32_t> nmap;
-  if (!dense) {
-    nmap.reserve((size_t)nn * 2);
-    for (uint32_t j = 0; j < nn; j++) nmap.emplace(h[j], j);
-  }
-  std::vector<uint32_t> padded((ix->h_start_ext.size() + 63) / 64 * 64, kNoSlot);
+  const bool dense = index_ids(h.data(), nn, nmap);
+  const uint32_t need = ix->start_ext_need();
+  std::vector<uint32_t> padded(need, kNoSlot);
+  // room for the committed copy of the overflow list (the writer's has it: the list does not grow here); a failure
+  // leaves the copy, and the index, as they were
+  SDB_TRY(ix->cm.grow_start_ext(need));
   // ---- swap in (nothing below can fail)
-  for (void *x : {(void *)ix->d_slab, (void *)ix->d_adj, (void *)ix->r_adj, (void *)ix->d_adjdist, (void *)ix->d_deg,
-                  (void *)ix->d_clean, (void *)ix->d_dcount, (void *)ix->d_ids, (void *)ix->r_ids})
-    (void)hipFree(x);
-  if (M) (void)hipFree(ix->d_codes);
-  if (had_ac) (void)hipFree(ix->d_adjcodes), (void)hipFree(ix->r_adjcodes), ix->d_adjcodes = nacw, ix->r_adjcodes = nacr;  // (NULL: dropped)
-  ac_guard.keep = true;
-  nb.keep = true;
-  ix->d_slab = nslab, ix->d_adj = nadj, ix->r_adj = nradj, ix->d_adjdist = nad, ix->d_deg = ndeg, ix->d_clean = nclean;
-  ix->d_dcount = ndc, ix->d_ids = nids, ix->r_ids = nrids;
-  if (M) ix->d_codes = ncodes;
-  (void)hipMemset(ix->d_dirty, 0, cap);
+  ix->adopt_row_tables(nb, t);
   ix->h_ids.swap(h);
   ix->id2slot.swap(nmap);
   ix->dense_ids = dense;
   if (ix->start_slot >= 0) ix->start_slot = (int64_t)map[(uint32_t)ix->start_slot];  // a flat index has none
-  for (auto &t : ix->h_start_ext) t = map[t];
+  for (auto &e : ix->h_start_ext) e = map[e];
   ix->n = nn, ix->n_dead = 0;
-  const uint32_t need = (uint32_t)((ix->h_start_ext.size() + 63) / 64 * 64);
   if (need) {  // both copies of the overflow list, renumbered
     std::copy(ix->h_start_ext.begin(), ix->h_start_ext.end(), padded.begin());
-    (void)hipMemcpy(ix->d_start_ext, padded.data(), (size_t)need * 4, hipMemcpyHostToDevice);
-    if (need > ix->r_start_ext_cap) {
-      if (ix->r_start_ext) (void)hipFree(ix->r_start_ext);
-      ix->r_start_ext = nullptr, ix->r_start_ext_cap = 0;
-      if (hipMalloc(&ix->r_start_ext, (size_t)need * 2 * 4) == hipSuccess) ix->r_start_ext_cap = need * 2;
-    }
-    if (ix->r_start_ext) (void)hipMemcpy(ix->r_start_ext, padded.data(), (size_t)need * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(ix->wr.start_ext, padded.data(), (size_t)need * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(ix->cm.start_ext, padded.data(), (size_t)need * 4, hipMemcpyHostToDevice);
   }
-  ix->view.n = nn, ix->view.adj = ix->r_adj, ix->view.ids = ix->r_ids, ix->view.start_ext = ix->r_start_ext;
-  ix->view.start_ext_n = (uint32_t)ix->h_start_ext.size();
-  ix->view.adj_codes = ix->r_adjcodes;
-  ix->view_gen++;
+  ix->publish();  // (no transaction is open: nothing of one to end)
   (void)hipDeviceSynchronize();
   ix->build_sketch(nullptr, 0, true);  // rows have moved (a stale copy is never used: sketch_gen); best-effort
   return SDB_OK;
@@ -1673,7 +994,7 @@ int sdb_index_export(const sdb_index *ix, uint64_t *ids, float *vectors, uint64_
   if (offsets || edges) {
     std::vector<uint32_t> adj((size_t)n * kAdjStride), deg(n);
     if (n) {
-      SDB_HIP(hipMemcpy(adj.data(), ix->d_adj, adj.size() * 4, hipMemcpyDeviceToHost));
+      SDB_HIP(hipMemcpy(adj.data(), ix->wr.adj, adj.size() * 4, hipMemcpyDeviceToHost));
       SDB_HIP(hipMemcpy(deg.data(), ix->d_deg, deg.size() * 4, hipMemcpyDeviceToHost));
     }
     uint64_t o = 0, k = 0;
@@ -1715,228 +1036,3 @@ SDB_API_CATCH("sdb_index_export")
 
 }  // extern "C"
 
-namespace sdb {
-int encode_bit_rows_public(sdb_index *ix, uint32_t first, uint32_t n, hipStream_t stream) {
-  return encode_bit_rows(ix, first, n, stream);
-}
-int store_rows_public(sdb_index *ix, uint32_t first, uint32_t n, const float *dev_vectors, hipStream_t stream) {
-  return store_rows(ix, first, n, dev_vectors, SDB_MEM_DEVICE, stream);
-}
-}  // namespace sdb
-
-namespace sdb {
-int unpermute_rows_public(const sdb_index *ix, uint32_t first, uint32_t n, float *dst, hipStream_t stream) {
-  if (n == 0) return SDB_OK;
-  const RowLayout &l = ix->lay;
-  hipLaunchKernelGGL(k_unpermute_rows, dim3(n), dim3(128), 0, stream, ix->d_slab + (size_t)first * l.ld, dst, n, l.dim,
-                     l.nblk, l.ng, l.ld);
-  SDB_HIP(hipGetLastError());
-  return SDB_OK;
-}
-}  // namespace sdb
-
-// productQuantizer.Set -> encode for every stored vector (product.go:161-169), then searches use the
-// LUT distance (product.go:250-277).
-// The write path keeps two things per row from its last robustPrune: how many leading edges came out of it
-// (d_clean: those do not dominate each other, build.hip) and the distances to them (d_dcount / d_adjdist).  Both
-// are statements about the store's distance function.  When that changes -- the store switches to the quantizer's
-// table distances, or centroid ids are overwritten -- they no longer hold and every row starts over.
-static int forget_prune_state(sdb_index *ix) {
-  if (ix->n == 0) return SDB_OK;
-  SDB_HIP(hipMemset(ix->d_clean, 0, (size_t)ix->n * sizeof(uint32_t)));
-  SDB_HIP(hipMemset(ix->d_dcount, 0, (size_t)ix->n * sizeof(uint32_t)));
-  return SDB_OK;
-}
-
-extern "C" int sdb_index_attach_pq(sdb_index *ix, const sdb_pq *pq, void *stream_) try {
-  if (!ix || !pq) return fail(SDB_ERR_INVALID, "NULL argument");
-  if (!pq->fitted) return fail(SDB_ERR_STATE, "quantizer is not fitted");
-  if (pq->dim != ix->lay.dim) return fail(SDB_ERR_INVALID, "quantizer dim %u != index dim %u", pq->dim, ix->lay.dim);
-  if (pq->device != ix->P.device) return fail(SDB_ERR_INVALID, "quantizer and index live on different devices");
-  {
-    // the reference swaps cosine for euclidean inside the quantizer only (product.go:52-61); any other
-    // mismatch between the index metric and the quantizer metric is a configuration error
-    const int want = ix->P.metric == SDB_METRIC_COSINE ? SDB_METRIC_EUCLIDEAN : (int)ix->P.metric;
-    if (pq->metric != want) return fail(SDB_ERR_INVALID, "quantizer metric does not match the index metric");
-  }
-  if (ix->bq) return fail(SDB_ERR_STATE, "a binary quantizer is attached");
-  if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open");
-  DeviceGuard dg(ix->P.device);
-  hipStream_t stream = as_stream(stream_);
-  // The hosts run Fit after a commit while their batcher keeps searching.  The new code rows are encoded into a
-  // buffer of their own while searches go on with what they have (full precision, or the previous quantizer's
-  // codes); then (quantizer, codes) change hands together under the exclusive lock, once the walks that were
-  // launched with the old pair have drained -- a search sees either pair whole, never the new tables over
-  // half-written codes, never freed rows.
-  uint8_t *ncodes = nullptr;
-  SDB_HIP(hipMalloc(&ncodes, (size_t)ix->cap * pq->M));
-  const uint32_t chunk = 1u << 18;
-  float *tmp = nullptr;
-  if (hipMalloc(&tmp, (size_t)std::min<uint32_t>(chunk, std::max<uint32_t>(ix->n, 1)) * ix->lay.dim * sizeof(float)) != hipSuccess) {
-    (void)hipFree(ncodes);
-    return fail(SDB_ERR_DEVICE, "out of device memory for the encode staging");
-  }
-  int rc = SDB_OK;
-  for (uint32_t first = 0; first < ix->n && rc == SDB_OK; first += chunk) {
-    const uint32_t m = std::min<uint32_t>(chunk, ix->n - first);
-    rc = unpermute_rows_public(ix, first, m, tmp, stream);
-    if (rc == SDB_OK) rc = pq_encode_device(pq, tmp, m, ncodes + (size_t)first * pq->M, stream);
-  }
-  (void)hipStreamSynchronize(stream);
-  (void)hipFree(tmp);
-  if (rc != SDB_OK) {
-    (void)hipFree(ncodes);
-    return rc;
-  }
-  std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
-  (void)hipDeviceSynchronize();  // walks launched with the old (quantizer, codes) pair
-  if (ix->d_codes) (void)hipFree(ix->d_codes);
-  ix->d_codes = ncodes;
-  ix->pq = pq;
-  ix->code_bytes = pq->M;
-  ix->drop_sketch();  // a quantized walk has no use for the float16 copy (sketch_supported)
-  // the neighbours' code rows behind the adjacency rows, for the new codes (M <= 32; index.h d_adjcodes)
-  SDB_TRY(ix->alloc_adjcodes());
-  SDB_TRY(ix->rebuild_adjcodes(stream));
-  return forget_prune_state(ix);
-}
-SDB_API_CATCH("sdb_index_attach_pq")
-
-// Centroid ids that do NOT come from encode(): the k-means labels productQuantizer.Fit leaves on its
-// training points (product.go:216-218) and the codes a bucket persisted under 'q' (product.go:349-383).
-extern "C" int sdb_index_set_codes(sdb_index *ix, uint64_t n, const uint64_t *ids, const uint8_t *codes) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (!ix->pq) return fail(SDB_ERR_STATE, "no quantizer attached");
-  // (code rows exist once, not per graph version: rewritten inside a transaction they could not be rolled back with it)
-  if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open: centroid ids are set outside it");
-  if (n == 0) return SDB_OK;
-  if (!ids || !codes) return fail(SDB_ERR_INVALID, "NULL argument");
-  const uint32_t M = ix->pq->M;
-  DeviceGuard dg(ix->P.device);
-  for (uint64_t i = 0; i < n; i++)  // nothing is written unless every id resolves
-    if (ix->slot_of(ids[i]) < 0) return fail(SDB_ERR_NOT_FOUND, "point %llu not found", (unsigned long long)ids[i]);
-  // code rows are rewritten in place: searches stand aside (exclusive lock) and the walks in flight drain first
-  std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
-  SDB_HIP(hipDeviceSynchronize());
-  // group runs of consecutive slots into one copy each (ids in storage order give one run)
-  uint64_t i = 0;
-  while (i < n) {
-    const int64_t s0 = ix->slot_of(ids[i]);
-    uint64_t j = i + 1;
-    while (j < n && ix->slot_of(ids[j]) == s0 + (int64_t)(j - i)) j++;
-    SDB_HIP(hipMemcpy(ix->d_codes + (size_t)s0 * M, codes + i * M, (j - i) * M, hipMemcpyHostToDevice));
-    i = j;
-  }
-  SDB_TRY(ix->rebuild_adjcodes(nullptr));  // every node that has one of these as a neighbour carries a copy of its code row
-  return forget_prune_state(ix);
-}
-SDB_API_CATCH("sdb_index_set_codes")
-
-extern "C" int sdb_index_get_codes(const sdb_index *ix, uint64_t n, const uint64_t *ids, uint8_t *codes) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (!ix->pq) return fail(SDB_ERR_STATE, "no quantizer attached");
-  if (n == 0) return SDB_OK;
-  if (!ids || !codes) return fail(SDB_ERR_INVALID, "NULL argument");
-  const uint32_t M = ix->pq->M;
-  DeviceGuard dg(ix->P.device);
-  uint64_t i = 0;
-  while (i < n) {
-    const int64_t s0 = ix->slot_of(ids[i]);
-    if (s0 < 0) return fail(SDB_ERR_NOT_FOUND, "point %llu not found", (unsigned long long)ids[i]);
-    uint64_t j = i + 1;
-    while (j < n && ix->slot_of(ids[j]) == s0 + (int64_t)(j - i)) j++;
-    SDB_HIP(hipMemcpy(codes + i * M, ix->d_codes + (size_t)s0 * M, (j - i) * M, hipMemcpyDeviceToHost));
-    i = j;
-  }
-  return SDB_OK;
-}
-SDB_API_CATCH("sdb_index_get_codes")
-
-// binaryQuantizer with a threshold (binary.go:131-139, 187-234): every stored point's BinaryVector in HBM, searches on
-// bitDistFn(encode(query), code), prunes on bitDistFn(code, code).  Without a threshold the quantizer is fitted first
-// (Fit, :145-185) from the index's own rows.
-extern "C" int sdb_index_attach_bq(sdb_index *ix, sdb_bq *bq, void *stream_) try {
-  if (!ix || !bq) return fail(SDB_ERR_INVALID, "NULL argument");
-  if (bq->dim != ix->lay.dim) return fail(SDB_ERR_INVALID, "quantizer dim %u != index dim %u", bq->dim, ix->lay.dim);
-  if (bq->device != ix->P.device) return fail(SDB_ERR_INVALID, "quantizer and index live on different devices");
-  if (ix->broken) return fail(SDB_ERR_STATE, "index is unusable after a failed write; reload it from the bucket");
-  if (ix->pq) return fail(SDB_ERR_STATE, "a product quantizer is attached");
-  if (ix->bq) return fail(SDB_ERR_STATE, "a binary quantizer is attached");
-  if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open");
-  if (!bq->has_thr && ix->n == ix->n_dead) return fail(SDB_ERR_STATE, "quantizer has no threshold and the index no rows to fit it from");
-  DeviceGuard dg(ix->P.device);
-  hipStream_t stream = as_stream(stream_);
-  // like attach_pq: the code rows are written into a buffer of their own while searches go on in full precision, then
-  // (quantizer, codes) change hands under the exclusive lock
-  const bool fitted_here = !bq->has_thr;
-  if (fitted_here) {  // Fit's first pass over the items in storage order, tombstones skipped (outside a transaction the writer's ids are the committed ones)
-    SDB_TRY(bq_fit_slab(ix->lay, ix->d_slab, ix->d_ids, ix->n, bq->d_thr, stream));
-    SDB_HIP(hipStreamSynchronize(stream));
-    bq->has_thr = true;
-  }
-  uint64_t *ncodes = nullptr;
-  hipError_t me = hipMalloc(&ncodes, (size_t)ix->cap * bq->W * 8);
-  int rc = me == hipSuccess ? bq_encode_slab(bq->d_thr, ix->lay, ix->d_slab, 0, ix->n, ncodes, stream)  // Fit's second pass / Set
-                            : fail(SDB_ERR_DEVICE, "hipMalloc failed: %s", hipGetErrorString(me));
-  (void)hipStreamSynchronize(stream);
-  if (rc != SDB_OK) {  // nothing changes hands: a quantizer fitted by this call is unfitted again
-    if (ncodes) (void)hipFree(ncodes);
-    if (fitted_here) bq->has_thr = false;
-    return rc;
-  }
-  std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
-  (void)hipDeviceSynchronize();  // walks launched on the float rows
-  ix->d_codes = reinterpret_cast<uint8_t *>(ncodes);
-  ix->bq = bq;
-  bq->attached = true;
-  ix->code_bytes = bq->W * 8;
-  ix->drop_sketch();  // a bit-code walk has no use for the float16 copy (sketch_supported)
-  return forget_prune_state(ix);
-}
-SDB_API_CATCH("sdb_index_attach_bq")
-
-// What a bucket holds under NodeKey(id, 'q') for a binary store (binaryQuantizedPoint.ReadFrom / WriteTo,
-// binary.go:275-310): ids [n], codes [n][W] u64, host memory.  The rules of sdb_index_set_codes.
-extern "C" int sdb_index_set_bit_codes(sdb_index *ix, uint64_t n, const uint64_t *ids, const uint64_t *codes) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (!ix->bq) return fail(SDB_ERR_STATE, "no binary quantizer attached");
-  if (ix->in_tx) return fail(SDB_ERR_STATE, "a write transaction is open: codes are set outside it");
-  if (n == 0) return SDB_OK;
-  if (!ids || !codes) return fail(SDB_ERR_INVALID, "NULL argument");
-  const size_t B = ix->code_bytes;
-  DeviceGuard dg(ix->P.device);
-  for (uint64_t i = 0; i < n; i++)  // nothing is written unless every id resolves
-    if (ix->slot_of(ids[i]) < 0) return fail(SDB_ERR_NOT_FOUND, "point %llu not found", (unsigned long long)ids[i]);
-  std::unique_lock<sdb::ViewMutex> wl(ix->view_mu);
-  SDB_HIP(hipDeviceSynchronize());
-  uint64_t i = 0;
-  while (i < n) {
-    const int64_t s0 = ix->slot_of(ids[i]);
-    uint64_t j = i + 1;
-    while (j < n && ix->slot_of(ids[j]) == s0 + (int64_t)(j - i)) j++;
-    SDB_HIP(hipMemcpy(ix->d_codes + (size_t)s0 * B, reinterpret_cast<const uint8_t *>(codes) + i * B, (j - i) * B, hipMemcpyHostToDevice));
-    i = j;
-  }
-  return forget_prune_state(ix);
-}
-SDB_API_CATCH("sdb_index_set_bit_codes")
-
-extern "C" int sdb_index_get_bit_codes(const sdb_index *ix, uint64_t n, const uint64_t *ids, uint64_t *codes) try {
-  if (!ix) return fail(SDB_ERR_INVALID, "index is NULL");
-  if (!ix->bq) return fail(SDB_ERR_STATE, "no binary quantizer attached");
-  if (n == 0) return SDB_OK;
-  if (!ids || !codes) return fail(SDB_ERR_INVALID, "NULL argument");
-  const size_t B = ix->code_bytes;
-  DeviceGuard dg(ix->P.device);
-  uint64_t i = 0;
-  while (i < n) {
-    const int64_t s0 = ix->slot_of(ids[i]);
-    if (s0 < 0) return fail(SDB_ERR_NOT_FOUND, "point %llu not found", (unsigned long long)ids[i]);
-    uint64_t j = i + 1;
-    while (j < n && ix->slot_of(ids[j]) == s0 + (int64_t)(j - i)) j++;
-    SDB_HIP(hipMemcpy(reinterpret_cast<uint8_t *>(codes) + i * B, ix->d_codes + (size_t)s0 * B, (j - i) * B, hipMemcpyDeviceToHost));
-    i = j;
-  }
-  return SDB_OK;
-}
-SDB_API_CATCH("sdb_index_get_bit_codes")

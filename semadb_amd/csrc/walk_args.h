@@ -54,7 +54,7 @@ struct SearchArgs {
   const float *pq_lut;
   const uint8_t *pq_codes;
   uint32_t pq_M, pq_K;
-  // != NULL: the code rows of every node's neighbours behind its adjacency row, [rows][64][M] (index.h d_adjcodes), for
+  // != NULL: the code rows of every node's neighbours behind its adjacency row, [rows][64][M] (index.h GraphCopy::adjcodes), for
   // the copy of the graph `adj` points at
   const uint8_t *adj_codes;
   uint32_t adj_rows;  // rows of `adj` (what tells an adjacency row from a chunk of the start node's overflow list)

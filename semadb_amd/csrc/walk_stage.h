@@ -120,7 +120,7 @@ struct HalfRows {
 };
 
 // The int8 format (SDB_TUNE_SKETCH = 3; cosine / dot, rows of 128 .. 384 floats): the index keeps
-// y8 = clamp(rint(y / s), -127, 127) of every row, one scale s per table (index.hip k_sketch8_rows), in place of the
+// y8 = clamp(rint(y / s), -127, 127) of every row, one scale s per table (index_sketch.hip k_sketch8_rows), in place of the
 // float16 copy -- half the bytes of the stage that reads a row for every edge of every hop.  A copy row is ld bytes; lane
 // L's 4 NG bytes of it are contiguous (bytes [4 NG L, 4 NG (L + 1)): group g's elements 4 L .. 4 L + 3 at + 4 g), so a
 // lane asks for a row with ONE load of NG dwords.

@@ -56,7 +56,7 @@ class Copy8:
         self.emax, self.ymax, self.rel = nanmax(e), nanmax(y), nanmax(rel)
 
     def refused(self):
-        """the table keeps the float16 copy (index.hip build_sketch_kind)"""
+        """the table keeps the float16 copy (index_sketch.hip build_sketch_kind)"""
         return not (self.emax <= MAX_RATIO * self.ymax) or not (self.rel <= MAX_RATIO)
 
 

@@ -47,7 +47,7 @@ def _index(vamana, metric, d, ex, wide_walk=1):
 
 def _walk(ix, queries, limit, L, mode, visit_cap=1024):
     """answers and the (discarded, contradicted) the call added.  Setting the knob clears the counters
-    (index.hip SDB_TUNE_SKETCH); mode None leaves it."""
+    (index.hip SDB_TUNE_SKETCH, index_sketch.hip); mode None leaves it."""
     if mode is not None:
         ix.set_tuning("sketch", mode)
     d0, c0, _ = ix.sketch_stats()
@@ -248,7 +248,7 @@ def _half_error_rows(rng, d):
 
 @pytest.mark.parametrize("metric", ["cosine", "euclidean"])
 def test_maxima_through_every_write_path(oracle, metric):
-    """The table-wide maxima max ||y - y16|| and max ||y16|| are carried from commit to commit (index.hip build_sketch,
+    """The table-wide maxima max ||y - y16|| and max ||y16|| are carried from commit to commit (index_sketch.hip build_sketch,
     `from` > 0) and restart only when every row is converted again (load, compact).  Rows that raise them, and small
     rows behind them (whose own maxima would lower them, were the carry lost), arrive through every write path; after
     each commit the device's count is inside the sandwich of the model's maxima over all rows converted since the last

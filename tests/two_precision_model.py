@@ -15,7 +15,7 @@ kept.  This module restates, in numpy and float64,
     lower        the same with every inflation the kernel documents charged on top, each rounded up generously.
 
 The kernel's derivation implies  lower <= discarded on the device <= upper <= discardable.  The constants of `lower`
-are the kernel's documented charges (walk_stage.h HalfRows::query, stage_eps, FirstStage::out / HalfRows::out_l2, index.hip k_sketch_rows), not its output.
+are the kernel's documented charges (walk_stage.h HalfRows::query, stage_eps, FirstStage::out / HalfRows::out_l2, index_sketch.hip k_sketch_rows), not its output.
 
 Also here: the inputs the GPU tests use (`width_case`, `l_case`, `hostile_queries`, `dispatch_case`), generated through one function so that the CPU
 test (test_two_precision_model.py) checks the model's own conditions on exactly them.
